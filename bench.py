@@ -14,6 +14,14 @@ shared inputs are broadcast from rank 0 once (untimed); per step the fitted thet
 all-gathered.  value = N * P / wall-clock per step (pts*outputs/s, whole job).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config north|eeg|dtc|small|ssm]
+                       [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (its kernel figures are
+the HIP-event spans of the timed steps themselves).  --full adds everything that takes runs of its
+own: the CPU baseline child, the self-checks against it and against fresh evaluations, the
+whole-chip and one-lane kernel probes, and the host->host steps (--h2h-steps).  --dump-outputs DIR
+writes what the last timed step returned (fitted thetas, -nlml, predicted means / stds) as
+DIR/<name>.npy.
 
 Launch: under torchrun (WORLD_SIZE set) every process is one rank.  Started directly with
 --gpus N > 1, the parent checks that N devices are visible (KFD topology in sysfs: it never
@@ -81,6 +89,47 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all series together (float64), under the 64 MB cap
+
+
+def dump_outputs(dirpath, small, series, rank=0):
+    """--dump-outputs: DIR/<name>.npy, float64.  `small` arrays are written whole.  `series` maps a
+    name to rows over the prediction points (a 2-D array / tensor, or a list of 1-D ones, numpy or
+    device); when all rows together exceed DUMP_BUDGET_BYTES every row is sampled at the same sorted
+    indices, drawn without replacement by a fixed seed (sample_index.npy).  Ranks > 0 of a multi-rank
+    job write <name>_rank<r>.npy."""
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+
+    def rows_of(v):
+        if isinstance(v, (list, tuple)):
+            return list(v)
+        return [v] if v.ndim == 1 else [v[i] for i in range(v.shape[0])]
+
+    series = {k: rows_of(v) for k, v in series.items()}
+    series = {k: v for k, v in series.items() if v}
+    n_rows = sum(len(v) for v in series.values())
+    n_pts = max([int(r.shape[0]) for v in series.values() for r in v] + [0])
+    idx = None
+    if n_rows and 8 * n_rows * n_pts > DUMP_BUDGET_BYTES:
+        keep = max(1, DUMP_BUDGET_BYTES // (8 * n_rows))
+        idx = np.sort(np.random.default_rng(0).choice(n_pts, size=keep, replace=False))
+        np.save(os.path.join(dirpath, f"sample_index{sfx}.npy"), idx.astype(np.float64))
+
+    def take(r):
+        if isinstance(r, np.ndarray):
+            return r if idx is None or r.shape[0] != n_pts else r[idx]
+        if idx is not None and r.shape[0] == n_pts:   # a device tensor: gather there, copy the sample
+            r = r[__import__("torch").from_numpy(idx).to(r.device)]
+        return r.detach().cpu().numpy()
+
+    for name, v in small.items():
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), np.asarray(v, dtype=np.float64))
+    for name, v in series.items():
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"),
+                np.stack([np.asarray(take(r), dtype=np.float64) for r in v]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,7 +141,16 @@ def main():
                     help="prediction estimator: analytic (S -> infinity limit), mc (the reference's "
                          "100-sample estimator, gpar_scaled_inference.jl:110-130), path (tmp.jl:"
                          "119-167: q(u) draws + posterior_rand paths of the time GP)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything that takes runs of its own: the CPU "
+                         "baseline child (unless --no-cpu-baseline), the self-checks, the whole-chip "
+                         "and one-lane kernel probes and the host->host steps (--h2h-steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy "
+                         "(float64: theta, nlml, means, stds, ...; series longer than the 64 MB "
+                         "budget allows are sampled at fixed seeded indices, sample_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline child (and the checks against it) out")
     ap.add_argument("--separate-predict", action="store_true",
                     help="gpar_fit then one gpar_predict per output (q(u) recomputes the Gram at the "
                          "fitted theta) instead of gpar_fit_predict (reuses the fit's Gram there)")
@@ -138,7 +196,7 @@ def main():
                          "258 GB per step costs ~5.8 s on MI355X (fresh VRAM is cleared); 'release': "
                          "the library default, freed when each fit call returns")
     ap.add_argument("--h2h-steps", type=int, default=2,
-                    help="after the timed device-resident steps, this many host->host steps "
+                    help="with --full: after the timed device-resident steps, this many host->host steps "
                          "(SURVEY §8d's unit: one pinned upload of t, Y, t*, F* and the pseudo-inputs "
                          "per step, means / stds downloaded), reported as host_to_host beside value")
     ap.add_argument("--schedule", default="",
@@ -166,7 +224,8 @@ def main():
     # the CPU baseline runs in a child process started before anything touches the GPU, so it
     # overlaps the inputs and the warm-up steps; it is joined before the timed region
     cpu_child = None
-    if (world0 == 1 and not args.no_cpu_baseline and args.shard is None and args.api == "batched"):
+    if (args.full and world0 == 1 and not args.no_cpu_baseline and args.shard is None
+            and args.api == "batched"):
         cpu_child = start_cpu_baseline(args)
 
     import torch
@@ -355,21 +414,24 @@ def main():
         res = {}
         if host:
             if problems:
-                fr, _, _ = fit_predict_outputs(ts_hh, Vs_h)
+                fr, means, stds = fit_predict_outputs(ts_hh, Vs_h)
                 last["fit"] = fr
+                last["returned"] = {"nlml": fr.nlml, "means": means, "stds": stds}
                 for i, p in enumerate(gpar_out):
                     res[p] = fr.theta[i]
             if y1_h is not None:
-                th1, _, _ = G.get_sde_predictions(t_hh, y1_h, ts_hh, "matern52", i_log_time_l=0.0,
-                                                  i_log_time_var=0.0, i_log_noise_sigma=-2.0,
-                                                  max_evals=EV, g_tol=-1.0, device=local)
+                th1, m1, v1 = G.get_sde_predictions(t_hh, y1_h, ts_hh, "matern52", i_log_time_l=0.0,
+                                                    i_log_time_var=0.0, i_log_noise_sigma=-2.0,
+                                                    max_evals=EV, g_tol=-1.0, device=local)
+                last["temporal"] = (m1, v1)
                 res[1] = np.array(list(th1) + [0.0, 0.0])
             return S.gather_thetas(res, P, dev)
         if chained and world == 1 and not shard_of:
-            fr, _, _ = G.fit_predict_batch(problems, x0, ts_d, [None] * len(problems),
-                                           max_evals=EV, g_tol=-1.0, mode=args.predict, samples=100,
-                                           seed=gpar_out[0], device=local, chain=chain_d,
-                                           chain_cols=[p - 1 for p in gpar_out])
+            fr, means, stds = G.fit_predict_batch(problems, x0, ts_d, [None] * len(problems),
+                                                  max_evals=EV, g_tol=-1.0, mode=args.predict,
+                                                  samples=100, seed=gpar_out[0], device=local,
+                                                  chain=chain_d, chain_cols=[p - 1 for p in gpar_out])
+            last["returned"] = {"nlml": fr.nlml, "means": means, "stds": stds}
             for i, p in enumerate(gpar_out):
                 res[p] = fr.theta[i]
         elif chained:
@@ -382,6 +444,7 @@ def main():
             if problems:
                 post = G.fit_posterior(problems, x0, max_evals=EV, g_tol=-1.0, device=local,
                                        keep=keep)
+                last["returned"] = {"nlml": post.fit.nlml}
                 for i, p in enumerate(gpar_out):
                     res[p] = post.theta[i]
             torch.cuda.synchronize()
@@ -415,10 +478,12 @@ def main():
             # get_gpar_scaled_predictions for every owned output: batched fit, then predictions
             fr, means, stds = fit_predict_outputs(ts_d, [Fs_d[:, : p - 1] for p in gpar_out])
             last["fit"], last["means"], last["stds"] = fr, means, stds
+            last["returned"] = {"nlml": fr.nlml, "means": means, "stds": stds}
             for i, p in enumerate(gpar_out):
                 res[p] = fr.theta[i]
         elif problems:
             fr = G.fit_batch(problems, x0, max_evals=EV, g_tol=-1.0, device=local)
+            last["returned"] = {"nlml": fr.nlml}
             for i, p in enumerate(gpar_out):
                 res[p] = fr.theta[i]
         if y1 is not None:
@@ -532,8 +597,20 @@ def main():
                           "only with keep (else it is released when each fit call returns)"}
     except Exception as e:   # noqa: BLE001
         memory = {"error": repr(e)}
+    if args.dump_outputs:
+        # what the last timed step returned to its caller (before any --full extra runs again)
+        ret = last.get("returned", {})
+        series = {k: ret[k] for k in ("means", "stds") if k in ret}
+        if "temporal" in last:
+            series["temporal_mean"], series["temporal_var"] = last["temporal"]
+        if chained:
+            series["chain"] = chain_d.T   # row p-1: output p's inference column (predicted means)
+        small = {"theta": theta}
+        if "nlml" in ret:
+            small["nlml"] = ret["nlml"]
+        dump_outputs(args.dump_outputs, small, series, rank)
     probe = None
-    if rank == 0 and cu_split and problems and not host and args.lanes == 1:
+    if args.full and rank == 0 and cu_split and problems and not host and args.lanes == 1:
         # after the timed region: the same kernels whole-chip (gpar_ctx_set_cu_split(ctx, 0)) in
         # a batched fit of four outputs around D = 32 (pipelined, distance cache), so the line
         # also carries the kernels' own fractions next to the split job's.  (A one-output fit
@@ -556,7 +633,8 @@ def main():
                      "note": "untimed, after the timed steps: a batched fit of these outputs with "
                              "the CU split off (whole-chip kernels), HIP events as above"}
     pred_probe = None
-    if rank == 0 and problems and not host and "fit" in last and args.predict == "analytic":
+    if (args.full and rank == 0 and problems and not host and "fit" in last
+            and args.predict == "analytic"):
         # after the timed region: two outputs' predictions one at a time (gpar_predict: one lane,
         # whole chip), so each prediction kernel's HIP-event time is its own duration, not a span
         # shared with the other lane's kernels as in the timed calls
@@ -581,7 +659,7 @@ def main():
                               "the fitted theta (one stream, whole chip), HIP events per kernel family "
                               "as roofline_predict")
     self_check = None
-    if rank == 0 and problems and "fit" in last:
+    if args.full and rank == 0 and problems and "fit" in last:
         # the timed steps' own outputs: each checked output's -nlml (the objective value the
         # split, cached, pipelined batched fit reached at its returned theta) against a fresh
         # single-output whole-chip evaluation at that theta (no split, no cache, no pipeline)
@@ -657,8 +735,9 @@ def main():
         self_check = dict(self_check or {}, cpu_port=port)
         self_check["ok"] = bool(self_check.get("ok", True) and port["ok"])
     h2h = None
-    if (rank == 0 and world == 1 and args.h2h_steps > 0 and problems and not host and not chained
-            and not temporal and not shard_of and not per_output and not args.separate_predict):
+    if (args.full and rank == 0 and world == 1 and args.h2h_steps > 0 and problems and not host
+            and not chained and not temporal and not shard_of and not per_output
+            and not args.separate_predict):
         # SURVEY §8d's host->host unit ("host->host wall-clock, excluding setup"): the
         # same job, every step starting from pinned host copies of its inputs -- t, Y (N x P), t*,
         # F* (N* x P) and the pseudo-inputs, one upload each into the buffers the problems view --
@@ -731,6 +810,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": el,
+            "full": bool(args.full),
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -943,7 +1023,7 @@ def stress_main(args):
     rank = int(os.environ.get("RANK", "0"))
     local = 0 if args.rehearse else int(os.environ.get("LOCAL_RANK", "0"))
     cpu_child = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cpu_child = start_cpu_baseline(args)   # before this process touches the GPU
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -1020,6 +1100,8 @@ def stress_main(args):
         el = float(e[0])
     fams = {k: ctx.kernel_stats(k) for k in ("gram", "whiten", "dist2", "fit_call", "fit_round")}
     works = {k: ctx.kernel_work(k) for k in ("gram", "whiten", "dist2")}
+    if args.dump_outputs and last.get("fit") is not None:   # this rank's fits (rows = its outputs)
+        dump_outputs(args.dump_outputs, {"theta": last["fit"].theta, "nlml": last["fit"].nlml}, {}, rank)
     evals_rank = len(problems) * EV
     evals_all = evals_rank
     if world > 1:
@@ -1046,8 +1128,8 @@ def stress_main(args):
             "metric": "GPAR-DTC objective evaluation throughput (pts\u00b7evaluations/s), "
                       f"N={D.fmt_count(N)} M={M} P={P}",
             "value": value, "unit": "pts\u00b7evaluations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": el, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "warmup": args.warmup, "ms_per_step": el, "full": bool(args.full),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic (toy_data.jl big-set functions extended to P outputs, generated on "
                     "the device with torch's seeded generator)",
             "config": {"workload": "GPAR-DTC per-evaluation (stress)", "N": N, "M": M, "P": P,

@@ -85,6 +85,49 @@ def test_visible_gpu_count_reads_kfd_topology(tmp_path):
     assert bench.visible_gpu_count(str(tmp_path / "absent"), env={}) == 0
 
 
+def test_dump_outputs_writes_whole_or_sampled_float64_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole; series over the budget sampled at the same fixed, sorted
+    indices in every row and on every call (numpy rows and torch rows alike)."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_dump_check", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 1000
+    means = [torch.arange(n, dtype=torch.float64) + 10 * i for i in range(3)]
+    stds = [m.numpy() * 2 for m in means]
+    temporal = torch.arange(2 * n, dtype=torch.float64).reshape(2, n)
+    theta = np.arange(20, dtype=np.float32).reshape(4, 5)
+
+    d0 = tmp_path / "whole"
+    bench.dump_outputs(str(d0), {"theta": theta}, {"means": means, "stds": stds, "tm": temporal})
+    assert sorted(os.listdir(d0)) == ["means.npy", "stds.npy", "theta.npy", "tm.npy"]
+    assert np.load(d0 / "theta.npy").dtype == np.float64
+    np.testing.assert_array_equal(np.load(d0 / "means.npy"), np.stack([m.numpy() for m in means]))
+    np.testing.assert_array_equal(np.load(d0 / "tm.npy"), temporal.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 8 * 100)   # 8 rows in all: 100 points each
+    d1, d2 = tmp_path / "s1", tmp_path / "s2"
+    for d in (d1, d2):
+        bench.dump_outputs(str(d), {"theta": theta}, {"means": means, "stds": stds, "tm": temporal})
+    idx = np.load(d1 / "sample_index.npy")
+    assert idx.dtype == np.float64 and idx.shape == (100,)
+    ii = idx.astype(np.int64)
+    assert np.all(np.diff(ii) > 0) and ii[0] >= 0 and ii[-1] < n
+    np.testing.assert_array_equal(np.load(d1 / "means.npy"), np.stack([m.numpy()[ii] for m in means]))
+    np.testing.assert_array_equal(np.load(d1 / "stds.npy"), np.stack([s[ii] for s in stds]))
+    np.testing.assert_array_equal(np.load(d1 / "tm.npy"), temporal.numpy()[:, ii])
+    for f in os.listdir(d1):
+        a, b = np.load(d1 / f), np.load(d2 / f)
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, b)
+    assert sum(os.path.getsize(d1 / f) for f in os.listdir(d1)) < 64 << 20
+    # ranks > 0 of a multi-rank job write beside rank 0's files
+    bench.dump_outputs(str(d1), {"theta": theta}, {}, rank=1)
+    assert (d1 / "theta_rank1.npy").exists()
+
+
 def test_launcher_fails_fast_when_a_rank_dies():
     """rank 1 exits with status 3 before its gather; rank 0 is then waiting in
     the gloo all_gather for it.  The launcher must notice, terminate rank 0 and return 3 well before

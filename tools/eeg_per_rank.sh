@@ -7,7 +7,7 @@ set -e
 TAG=${1:-eeg}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-timeout -k 10 240 python -u bench.py --config eeg --steps 2 --warmup 1 > "$OUT/eeg_1gpu.json" 2> "$OUT/eeg_1gpu.err"
+timeout -k 10 240 python -u bench.py --full --config eeg --steps 2 --warmup 1 > "$OUT/eeg_1gpu.json" 2> "$OUT/eeg_1gpu.err"
 for R in 0 3 7; do
   for INF in given chained; do
     timeout -k 10 240 python -u bench.py --config eeg --shard $R/8 --inference $INF --steps 3 --warmup 1 \

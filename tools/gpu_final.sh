@@ -1,5 +1,5 @@
 # Round evidence: full GPU suite, smoke, PMC passes, rocprof kernel stats of the north bench, and
-# the default bench line (with cpu_baseline).  bash tools/gpu_final.sh <tag>, e.g. r04z: every
+# the --full bench line (with cpu_baseline).  bash tools/gpu_final.sh <tag>, e.g. r04z: every
 # summary lands under gpurun_out/final_<tag>/ named as profiles/ wants it.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
@@ -18,5 +18,5 @@ PMC=$(python3 -c "import re;print(re.search(r'PMC_FILE = \"(.*)\"', open('bench.
 cp gpurun_out/pmc/summary.json profiles/$PMC
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_${TAG}_north_rocprof_run.json 2> $OUT/bench_rocprof.err || { echo ROCPROF BENCH FAILED; tail -20 $OUT/bench_rocprof.err; exit 1; }
 find gpurun_out/prof -name '*kernel_stats.csv' -exec cp {} $OUT/rocprof_bench_${TAG}_north_stats.csv \;
-timeout -k 10 600 python bench.py > $OUT/bench_${TAG}_north.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench_${TAG}_north.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench_${TAG}_north.json

@@ -11,7 +11,7 @@ if [ $# -gt 0 ]; then
   timeout -k 10 900 python -u -m pytest "$@" -x -v --timeout 300 --timeout-method thread > $O/pytest.txt 2>&1 || { echo PYTEST FAILED; tail -30 $O/pytest.txt; exit 1; }
   tail -1 $O/pytest.txt
 fi
-timeout -k 10 200 python bench.py --config ssm --steps 5 --warmup 2 > $O/ssm.json 2> $O/ssm.err || exit 1
+timeout -k 10 200 python bench.py --full --config ssm --steps 5 --warmup 2 > $O/ssm.json 2> $O/ssm.err || exit 1
 timeout -k 10 200 python bench.py --config eeg --shard 0/8 --steps 3 --warmup 1 > $O/eeg_s0.json 2> $O/eeg_s0.err || exit 1
 EVALS=50 BENCH_ARGS="--config eeg --shard 0/8" bash tools/gpu_trace_head.sh $TAG/trace_eeg > $O/trace_eeg.txt 2>&1 || exit 1
 python3 -c "

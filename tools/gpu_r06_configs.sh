@@ -7,7 +7,7 @@ O=gpurun_out/${1:?tag}
 mkdir -p $O
 run() {  # name, seconds, bench args...
   local name=$1 secs=$2; shift 2
-  timeout -k 10 $secs python -u bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name FAILED"; tail -5 $O/$name.err; exit 1; }
+  timeout -k 10 $secs python -u bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name FAILED"; tail -5 $O/$name.err; exit 1; }
 }
 run stress_shard0of8 600 --config stress --shard 0/8 --steps 2 --warmup 1
 run stress_shard7of8 600 --config stress --shard 7/8 --steps 1 --warmup 1 --no-cpu-baseline

@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_schedule.py tests/test_gpu_
 tail -1 $O/pytest.txt
 run() {  # name, seconds, bench args...
   local name=$1 secs=$2; shift 2
-  timeout -k 10 $secs python -u bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name FAILED"; tail -5 $O/$name.err; exit 1; }
+  timeout -k 10 $secs python -u bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name FAILED"; tail -5 $O/$name.err; exit 1; }
 }
 run dtc 200 --config dtc --steps 3 --warmup 1
 run eeg 300 --config eeg --steps 2 --warmup 1
