@@ -79,10 +79,11 @@ struct gpar_ctx {
   };
   std::vector<Staging> stage;   // one per output group (deque-like: grown before use, never moved after)
   Staging* staging = nullptr;
-  bool overlap = true;            // "overlap": round-overlapping batched fit (gpar_ctx_set_fit_overlap)
+  // (the knobs are ints, flags 0 / 1 among them: one table names them all, kKnobs in host_api.cpp)
+  int overlap = 1;                // "overlap": round-overlapping batched fit (gpar_ctx_set_fit_overlap)
   int predict_lanes = 2;          // "predict_lanes": gpar_fit_predict's predictions over 1 or 2 streams
-  bool predict_fused = true;      // "predict_fused": predict_var (off: predict_rows + gemm_nt; last bits differ)
-  bool qu_batch = true;           // "qu_batch": gpar_fit_predict's q(u) batched over the outputs
+  int predict_fused = 1;          // "predict_fused": predict_var (off: predict_rows + gemm_nt; last bits differ)
+  int qu_batch = 1;               // "qu_batch": gpar_fit_predict's q(u) batched over the outputs
   // "dense_early": the G-independent dense tail ahead of a split round's Grams on the Gram stream
   // (1), or after the Grams (0)
   int dense_early = 1;
@@ -91,9 +92,6 @@ struct gpar_ctx {
   // "gram_group": outputs per grouped Gram launch set in an unsplit batched fit of small problems
   // (run_gram_stage): 0 = off, >= 2 that many, 1 = off, -1 = auto (kGramGroupAuto below)
   int gram_group = -1;
-  // set by eval_dtc when the round's dense prefix runs on s_d: the round's first Gram waits for it
-  // (beside a Gram the latency-bound 64 x 64 launches slowed it 4.4 -> 5.3 ms at the eeg shard)
-  hipEvent_t gram_after = nullptr;
   // "fit_chunks": outputs per consecutive sub-batch of a gpar_fit whose distances the cache
   // cannot all hold at once (fit_impl): -1 = auto (unpipelined fits of outputs with D >= 17, the
   // stress config), 0 = off (one batch), k >= 1 = sub-batches of k outputs
@@ -113,7 +111,7 @@ struct gpar_ctx {
   // "serialize": side, s_w, s_g, s_g2 and s_d all alias `main`, so every launch runs in issue order
   // on one stream (the created streams stay in own_*): the order-free reference the concurrent
   // schedule must equal bit for bit.  Plans, CU shares of work items and workspaces are unchanged.
-  bool serialize = false;
+  int serialize = 0;
   // own_s: s_w, s_g, s_g2 and s_d (the round overlap's dense tails and gains, on the whitening CUs)
   hipStream_t own_side = nullptr, own_s[4] = {nullptr, nullptr, nullptr, nullptr};
   std::string ws_suffix;          // appended to workspace names (a prediction lane's own buffers)
@@ -295,6 +293,23 @@ inline const double* cached_d2(const gpar_ctx* c, const DevProblem& p) {
 }
 bool shares_grid(const std::vector<DevProblem>& P);
 bool fit_pipelined(const gpar_ctx* c, const std::vector<DevProblem>& P, bool fix_beta = false);
+inline int64_t max_mp(const std::vector<DevProblem>& P) {   // the batch's widest padded M
+  int64_t mpmax = 0;
+  for (const auto& p : P) mpmax = std::max(mpmax, p.mp);
+  return mpmax;
+}
+// The schedule a batch's Gram stage takes (run_gram_stage), decided here and nowhere else: what
+// runs beside the stage (eval_dtc's dense prefix, the fit's round overlap, the distance cache's
+// width rule, the workspace estimate) reads the same plan, so none of them can disagree with it.
+struct StagePlan {
+  int64_t mpmax = 0;
+  bool shared = false;      // one batched gains launch serves every output (shares_grid)
+  bool pipelined = false;   // whitening ahead of the previous Gram, two betas (fit_pipelined)
+  bool split = false;       // pipelined on the CU split (split_active): SplitPipe
+  int nlanes = 1;           // streams the outputs alternate over (gpar_ctx::lanes)
+  int gram_group = 0;       // outputs per grouped Gram launch set; 0: per-output Grams
+};
+StagePlan stage_plan(const gpar_ctx* c, const std::vector<DevProblem>& P, bool fix_beta = false);
 void check_sorted_host(const double* t, int64_t n);
 void check_problem(const gpar_problem& p);
 void check_batch(const gpar_problem* probs, int nprob);
@@ -309,6 +324,18 @@ std::pair<const double*, int64_t> upload_shared_block(gpar_ctx* c, const std::st
 struct Theta {
   double l_t, sv_t, l_o, sv_o, sigma;
 };
+inline double unpack(double p) { return std::exp(p) + 1e-3; }
+// a simplex point (log scale) as hyperparameters
+inline Theta theta_of(const std::vector<double>& x) {
+  return {unpack(x[0]), unpack(x[1]), unpack(x[2]), unpack(x[3]), unpack(x[4])};
+}
+// the time chain of an output at th, observation noise sigma^2
+inline ChainParamsHost chain_params_of(const Theta& th, double s2) {
+  return {1.0 / th.l_t, th.l_t, th.sv_t * th.sv_t, s2};
+}
+inline ChainParamsHost chain_params_of(const Theta& th) {
+  return chain_params_of(th, th.sigma * th.sigma);
+}
 
 // --------------------------------------------------------------------------- gains
 struct GainsOut {
@@ -337,6 +364,15 @@ struct GainsPlan {
   double* moments = nullptr;   // chains_logpdf: per-chunk data moments instead of records
   void launch(hipStream_t st, int first, int count) const;
 };
+// output i's slice of a batched gains pass over chains of nch chunks
+inline GainsOut slice_gains(const GainsOut& g, int i, int64_t nch) {
+  GainsOut s = g;
+  s.rec = g.rec + (size_t)i * g.recstride;
+  s.g = g.g + (size_t)i * g.gstride;
+  s.phi = g.phi + (size_t)i * g.phistride;
+  s.logs = g.logs + (size_t)i * nch;
+  return s;
+}
 GainsPlan plan_gains(gpar_ctx* c, int sdim, const double* t, int64_t n,
                      const std::vector<ChainParamsHost>& cps, const double* noise, bool want_pf,
                      const std::string& tag, const std::vector<const double*>* ys = nullptr,
@@ -373,7 +409,8 @@ StageBufs stage_bufs(gpar_ctx* c, int l, int64_t n, int64_t mpmax);
 // One output-evaluation in the Gram stage: the problem at hyperparameters th with its gains;
 // alpha = L_Sigma^-1 y (asend: its chunk end states from the batched gains pass, which filtered
 // alpha_loc already; null: alpha is whitened in stage_post into alpha); where G / r / the
-// alpha^2 partials go.  group / last: the round-overlapping fit's bookkeeping.
+// alpha^2 partials go.  group / last: the round-overlapping fit's bookkeeping.  after: the slot of
+// the stage's pending dense-prefix event, which its first Gram takes (wait_dense_prefix).
 struct StageJob {
   const DevProblem* p = nullptr;
   const Theta* th = nullptr;
@@ -384,6 +421,7 @@ struct StageJob {
   int64_t ldg = 0;
   int group = -1;
   bool last = false;
+  hipEvent_t* after = nullptr;
 };
 void stage_whiten(gpar_ctx* c, const StageJob& j, const StageBufs& b);
 void stage_post(gpar_ctx* c, const StageJob& j, const StageBufs& b, bool fix_beta);
@@ -477,8 +515,10 @@ struct SplitPipe {
     HIPCHECK(hipStreamWaitEvent(st, c->ev_sp, 0));
   }
 };
+// after: an event the stage's first Gram waits for on its stream (eval_dtc's dense prefix)
 GramOut run_gram_stage(gpar_ctx* c, const std::vector<DevProblem>& P,
-                              const std::vector<Theta>& th, bool fix_beta = false);
+                       const std::vector<Theta>& th, bool fix_beta = false,
+                       hipEvent_t after = nullptr);
 
 // --------------------------------------------------------------------------- dense tail
 struct DenseOut {
@@ -502,7 +542,6 @@ std::vector<Theta> thetas_from(const double* theta, int np);
 // async (the unsplit round overlap, fit_overlapped_unsplit): the values and Cholesky status
 // flags go to pinned host memory by async copies, `done` is recorded after them and eval_dtc
 // returns without waiting (out / status_out untouched)
-bool grouped_gram_eligible(gpar_ctx* c, const std::vector<DevProblem>& P);
 struct EvalAsync {
   double* hout = nullptr;   // pinned, one value per problem
   int* hstat = nullptr;     // pinned, two flags per problem
@@ -511,7 +550,6 @@ struct EvalAsync {
 void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<Theta>& th,
                      double* out, std::vector<int>& status_out, GramOut* gram_out = nullptr,
                      const EvalAsync* async = nullptr);
-
 
 struct QuOut {
   double *me, *cov, *Ucol;
@@ -568,7 +606,6 @@ std::vector<QuPre> run_q_u_batch(gpar_ctx* c, const std::vector<DevProblem>& P,
 void chains_logpdf(gpar_ctx* c, const std::vector<const double*>& ys, int64_t n, const double* t,
                    int sdim, const double* theta, double* lml);
 
-
 // --------------------------------------------------------------------------- posterior paths
 // The path draws of a seed are decorrelated from its q(u) draws (gpar_path_normals exports them).
 constexpr uint64_t kPathSeedXor = 0x5851F42D4C957F2Dull;
@@ -587,7 +624,6 @@ void chains_smooth(gpar_ctx* c, int nchains, int64_t n, const double* t, const d
                           int64_t ldo);
 std::vector<ChainParamsHost> chain_params(const double* theta, int nchains);
 
-inline double unpack(double p) { return std::exp(p) + 1e-3; }
 void enter(gpar_ctx* c);
 int fail(gpar_ctx* c, int code, const char* what);
 int64_t fit_ws_estimate(const gpar_ctx* c, const std::vector<DevProblem>& P);
@@ -600,7 +636,6 @@ void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* lo
                      int32_t* evals_out, FitKeep* keep, int64_t later_bytes = 0);
 
 }  // namespace gpar
-
 
 #define API_BEGIN(ctx)                                          \
   if (!(ctx)) return GPAR_ERR_STATE;                            \

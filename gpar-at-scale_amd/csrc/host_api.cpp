@@ -2,6 +2,7 @@
 #include "host.hpp"
 
 #include <cctype>
+#include <climits>
 
 namespace gpar {
 
@@ -80,83 +81,61 @@ static int set_cu_split(gpar_ctx* c, int w, bool forced) {
   return GPAR_OK;
 }
 
-// Every knob's non-default values are supported modes (round 5 deleted the A/B-only ones: the
-// split round head's variants, the dense prefix on a stream of its own, the DG share, the round
-// overlap's tail placement and the prediction's distance-pass whitening, each measured slower).
-static constexpr const char* kScheduleKnobs[] = {"overlap", "overlap_group", "predict_fused",
-                                                  "qu_batch", "dense_early", "predict_lanes",
-                                                  "serialize", "post_gram", "compact_rec",
-                                                  "dg_rows_w", "gram_group", "fit_chunks",
-                                                  "device_nm"};
+// The schedule knobs (gpar_ctx_set_schedule / gpar_ctx_get_schedule; GPAR_<KNOB> in the
+// environment at creation, applied in this order): a value in [lo, hi] or `extra`.  Flags take
+// any value (non-zero = on).  Every knob's non-default values are supported modes (round 5
+// deleted the A/B-only ones: the split round head's variants, the dense prefix on a stream of its
+// own, the DG share, the round overlap's tail placement and the prediction's distance-pass
+// whitening, each measured slower).
+struct Knob {
+  const char* name;
+  int gpar_ctx::*field;
+  int lo, hi, extra;
+  bool flag = false;
+};
+static constexpr Knob kKnobs[] = {
+    {"overlap", &gpar_ctx::overlap, 0, 1, 0, true},
+    {"overlap_group", &gpar_ctx::overlap_group, 0, INT_MAX, 0},
+    {"predict_fused", &gpar_ctx::predict_fused, 0, 1, 0, true},
+    {"qu_batch", &gpar_ctx::qu_batch, 0, 1, 0, true},
+    {"dense_early", &gpar_ctx::dense_early, 0, 1, 0},
+    {"predict_lanes", &gpar_ctx::predict_lanes, 1, 2, 1},
+    {"serialize", &gpar_ctx::serialize, 0, 1, 0, true},
+    {"post_gram", &gpar_ctx::post_gram, -1, 1, 0},
+    {"compact_rec", &gpar_ctx::compact_rec, -1, 1, 0},
+    {"dg_rows_w", &gpar_ctx::dg_rows_w, -50, 100, kDgRowsAuto},
+    {"gram_group", &gpar_ctx::gram_group, -1, 64, 0},
+    {"fit_chunks", &gpar_ctx::fit_chunks, -1, 4096, 0},
+    {"device_nm", &gpar_ctx::device_nm, 0, 1, 0},
+};
+static const Knob* find_knob(const std::string& k) {
+  for (const Knob& kn : kKnobs)
+    if (k == kn.name) return &kn;
+  return nullptr;
+}
 
-// gpar_ctx_set_schedule / gpar_ctx_get_schedule (GPAR_ERR_ARG: unknown knob or value).
+// GPAR_ERR_ARG: unknown knob or value.
 static int set_schedule(gpar_ctx* c, const std::string& k, int v) {
-  if (k == "overlap") c->overlap = v != 0;
-  else if (k == "overlap_group") {
-    if (v < 0) return GPAR_ERR_ARG;
-    c->overlap_group = v;
-  }
-  else if (k == "predict_fused") c->predict_fused = v != 0;
-  else if (k == "qu_batch") c->qu_batch = v != 0;
-  else if (k == "dense_early") {
-    if (v < 0 || v > 1) return GPAR_ERR_ARG;
-    c->dense_early = (int)v;
-  }
-  else if (k == "dg_rows_w") {
-    if ((v < -50 || v > 100) && v != kDgRowsAuto) return GPAR_ERR_ARG;
-    c->dg_rows_w = v;
-  } else if (k == "compact_rec") {
-    if (v < -1 || v > 1) return GPAR_ERR_ARG;
-    c->compact_rec = v;
-  }
-  else if (k == "gram_group") {
-    if (v < -1 || v > 64) return GPAR_ERR_ARG;
-    c->gram_group = v;
-  }
-  else if (k == "fit_chunks") {
-    if (v < -1 || v > 4096) return GPAR_ERR_ARG;
-    c->fit_chunks = v;
-  }
-  else if (k == "device_nm") {
-    if (v < 0 || v > 1) return GPAR_ERR_ARG;
-    c->device_nm = v;
-  }
-  else if (k == "post_gram") {
-    if (v < -1 || v > 1) return GPAR_ERR_ARG;
-    c->post_gram = v;
-  }
-  else if (k == "predict_lanes") {
-    if (v != 1 && v != 2) return GPAR_ERR_ARG;
-    c->predict_lanes = v;
-  } else if (k == "serialize") {
+  const Knob* kn = find_knob(k);
+  if (!kn) return GPAR_ERR_ARG;
+  if (kn->flag) v = v != 0;
+  else if ((v < kn->lo || v > kn->hi) && v != kn->extra) return GPAR_ERR_ARG;
+  if (kn->field == &gpar_ctx::serialize) {
     // the streams about to be re-routed must not hold queued work
     (void)hipStreamSynchronize(c->main);
     (void)hipStreamSynchronize(c->own_side);
     for (hipStream_t st : c->own_s)
       if (st) (void)hipStreamSynchronize(st);
-    c->serialize = v != 0;
-    route_streams(c);
-  } else {
-    return GPAR_ERR_ARG;
   }
+  c->*kn->field = v;
+  if (kn->field == &gpar_ctx::serialize) route_streams(c);
   return GPAR_OK;
 }
 
 static int get_schedule(const gpar_ctx* c, const std::string& k, int32_t* v) {
-  if (k == "overlap") *v = c->overlap;
-  else if (k == "overlap_group") *v = c->overlap_group;
-  else if (k == "predict_fused") *v = c->predict_fused;
-  else if (k == "qu_batch") *v = c->qu_batch;
-  else if (k == "dense_early") *v = c->dense_early;
-  else if (k == "post_gram") *v = c->post_gram;
-  else if (k == "compact_rec") *v = c->compact_rec;
-  else if (k == "dg_rows_w") *v = c->dg_rows_w;
-  else if (k == "gram_group") *v = c->gram_group;
-  else if (k == "fit_chunks") *v = c->fit_chunks;
-  else if (k == "device_nm") *v = c->device_nm;
-  else if (k == "predict_lanes") *v = c->predict_lanes;
-  else if (k == "serialize") *v = c->serialize;
-  else return GPAR_ERR_ARG;
+  const Knob* kn = find_knob(k);
+  if (!kn) return GPAR_ERR_ARG;
+  *v = c->*kn->field;
   return GPAR_OK;
 }
 }  // namespace gpar
@@ -187,10 +166,10 @@ int32_t gpar_ctx_create(int32_t device, gpar_ctx** out) {
   c->stream = c->main;
   route_streams(c);
   // schedule knobs from the environment (GPAR_OVERLAP=0, GPAR_SERIALIZE=1, ...)
-  for (const char* k : kScheduleKnobs) {
+  for (const Knob& kn : kKnobs) {
     std::string env = "GPAR_";
-    for (const char* q = k; *q; ++q) env += (char)std::toupper((unsigned char)*q);
-    if (const char* e = std::getenv(env.c_str())) (void)set_schedule(c, k, std::atoi(e));
+    for (const char* q = kn.name; *q; ++q) env += (char)std::toupper((unsigned char)*q);
+    if (const char* e = std::getenv(env.c_str())) (void)set_schedule(c, kn.name, std::atoi(e));
   }
   // GPAR_SPLIT_CUS overrides the default CU split
   const char* e_split = std::getenv("GPAR_SPLIT_CUS");

@@ -124,9 +124,7 @@ bool shares_grid(const std::vector<DevProblem>& P) {
 // buffers (only when a second beta fits comfortably: the north job's 4.1 GB, not the N = 1e7,
 // M = 1024 stress config's 82 GB).  The CU split and the all-D distance cache apply only on top of it.
 bool fit_pipelined(const gpar_ctx* c, const std::vector<DevProblem>& P, bool fix_beta) {
-  int64_t mpmax = 0;
-  for (auto& p : P) mpmax = std::max(mpmax, p.mp);
-  const int64_t beta_bytes = (P[0].n + 16) * mpmax * (int64_t)sizeof(double);
+  const int64_t beta_bytes = (P[0].n + 16) * max_mp(P) * (int64_t)sizeof(double);
   return P.size() > 1 && !fix_beta && c->lanes == 1 && shares_grid(P) &&
          beta_bytes <= kPipeMaxBetaBytes;
 }

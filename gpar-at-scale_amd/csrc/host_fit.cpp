@@ -30,12 +30,11 @@ constexpr int64_t kDistCacheSplitMinN = (int64_t)1 << 16;
 // the kept Grams): the cache's auto budget leaves room for them.
 int64_t fit_ws_estimate(const gpar_ctx* c, const std::vector<DevProblem>& P) {
   const int64_t np = (int64_t)P.size(), n = P[0].n, nch = (n + kChunk - 1) / kChunk;
-  int64_t mpmax = 0, rs = 4;
-  for (auto& p : P) {
-    mpmax = std::max(mpmax, p.mp);
-    rs = std::max<int64_t>(rs, rec_size(p.sdim));
-  }
-  const int64_t nbuf = (fit_pipelined(c, P) || c->lanes > 1) ? 2 : 1;
+  const StagePlan sp = stage_plan(c, P);
+  const int64_t mpmax = sp.mpmax;
+  int64_t rs = 4;
+  for (auto& p : P) rs = std::max<int64_t>(rs, rec_size(p.sdim));
+  const int64_t nbuf = (sp.pipelined || c->lanes > 1) ? 2 : 1;
   const GramPlan pl = gram_plan(n, mpmax, false, 256, 256);
   const int64_t doubles = nbuf * ((n + 16) * mpmax + n + 3 * nch * (mpmax + 1) * 4)   // beta, carries
                           + np * n * (rs + 5)                 // gains records, fix-up rows, alpha
@@ -87,12 +86,10 @@ std::vector<DevProblem> attach_dist_cache(gpar_ctx* c, const std::vector<DevProb
   std::vector<int> order(P.size());
   for (size_t i = 0; i < P.size(); ++i) order[i] = (int)i;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return P[a].d > P[b].d; });
-  int64_t mpmax = 0;
-  for (auto& p : P) mpmax = std::max(mpmax, p.mp);
   // every output (D >= 1) only where the whitening runs on the CU split's quarter of the chip,
-  // i.e. the pipelined split schedule actually runs (fit_pipelined && split_active)
-  const int64_t min_d = (fit_pipelined(c, P) && split_active(c, P[0].n, mpmax) &&
-                         P[0].n >= kDistCacheSplitMinN) ? kDistCacheMinDSplit : kDistCacheMinD;
+  // i.e. the pipelined split schedule actually runs (StagePlan::split)
+  const int64_t min_d = (stage_plan(c, P).split && P[0].n >= kDistCacheSplitMinN)
+                            ? kDistCacheMinDSplit : kDistCacheMinD;
   int slot = 0;
   for (int i : order) {
     const DevProblem& p = P[i];
@@ -143,19 +140,101 @@ std::vector<DevProblem> attach_dist_cache(gpar_ctx* c, const std::vector<DevProb
 // (batched gains and dense-tail launches compute each problem independently), so the fit equals
 // the round-by-round one bit for bit.  Uploads go through pinned arenas (gpar_ctx::staging): a
 // pageable copy queued behind running work could block the host and stall the pipeline.
-struct OverlapGroup {
+// What both round overlaps (fit_overlapped, fit_overlapped_unsplit) keep per output group.  They
+// share the protocol: deal the outputs (deal_groups), carve each group a pinned arena
+// (group_result_arena), then take the groups in turn (run_groups): wait for a group's values,
+// tell its simplices (tell_group), ask them for the next points (ask_group), queue that round.
+struct RoundGroup {
   int id = 0;
   std::vector<int> members;        // output indices dealt to this group
   std::vector<int> act;            // this round's active members
   std::vector<Theta> th;           // their hyperparameters this round
   std::vector<DevProblem> sub;     // their problems (stable while their jobs are queued)
   GramOut go{};                    // one G / r / alpha^2 / log S slot per member
-  double *alpha_all = nullptr, *asend_all = nullptr, *dout = nullptr;
   double* hout = nullptr;          // pinned: -dtc values of the round
   int* hstat = nullptr;            // pinned: Cholesky status flags (2 per output)
   size_t res_bytes = 0;            // the arena's result prefix
   bool in_flight = false;
 };
+
+using AcceptFn = std::function<void(int, double, const double*, const double*, int64_t)>;
+
+// K groups, the outputs dealt round-robin
+template <class Group>
+static std::vector<Group> deal_groups(int np, int K) {
+  std::vector<Group> grp(K);
+  for (int g = 0; g < K; ++g) grp[g].id = g;
+  for (int i = 0; i < np; ++i) grp[i % K].members.push_back(i);
+  return grp;
+}
+
+// Group G's pinned arena (gpar_ctx::stage[G.id], grown to fit; no arena is in use between calls):
+// the round's values and status flags first (hout, hstat: res_bytes), the round's uploads behind.
+static void group_result_arena(gpar_ctx* c, RoundGroup& G) {
+  if ((int)c->stage.size() <= G.id) c->stage.resize(G.id + 1);
+  gpar_ctx::Staging& s = c->stage[G.id];
+  const size_t cap = G.members.size();
+  const size_t vbytes = (cap * sizeof(double) + 255) & ~(size_t)255;
+  G.res_bytes = vbytes + ((2 * cap * sizeof(int) + 255) & ~(size_t)255);
+  const size_t need = G.res_bytes + ((size_t)1 << 20) + cap * 4096;
+  if (s.cap < need) {
+    if (s.host) HIPCHECK(hipHostFree(s.host));
+    s.host = nullptr;
+    s.cap = 0;
+    HIPCHECK(hipHostMalloc((void**)&s.host, need, hipHostMallocDefault));
+    s.cap = need;
+  }
+  G.hout = reinterpret_cast<double*>(s.host);
+  G.hstat = reinterpret_cast<int*>(s.host + vbytes);
+}
+
+// Ask every member still running for its next point (act, th, sub) and reset the group's upload
+// arena: the previous round's uploads have been consumed.  False: no member is active.
+static bool ask_group(gpar_ctx* c, RoundGroup& G, std::vector<NelderMead>& nm,
+                      const std::vector<DevProblem>& P) {
+  G.act.clear();
+  G.th.clear();
+  G.sub.clear();
+  for (int i : G.members)
+    if (!nm[i].done()) {
+      G.act.push_back(i);
+      G.th.push_back(theta_of(nm[i].ask()));
+      G.sub.push_back(P[i]);
+    }
+  c->stage[G.id].used = G.res_bytes;
+  return !G.act.empty();
+}
+
+// what a simplex is told: INFINITY (point rejected) after a PosDefException or a non-finite value
+static double told_value(double dtc, bool failed) {
+  const double f = -dtc;
+  return failed || !std::isfinite(f) ? INFINITY : f;
+}
+
+// Hand a finished round's values (and Gram slots, for kept points: on c->stream) to the simplices.
+static void tell_group(RoundGroup& G, const AcceptFn& accept) {
+  const int64_t ld = G.go.ldg;
+  for (size_t a = 0; a < G.act.size(); ++a)
+    accept(G.act[a], told_value(G.hout[a], G.hstat[2 * a] || G.hstat[2 * a + 1]),
+           G.go.G + a * ld * ld, G.go.r + a * ld, ld);
+  G.in_flight = false;
+}
+
+// Queue every group's first round, then take the groups in turn while any has a round in flight.
+template <class Group, class Finish, class Begin>
+static void run_groups(std::vector<Group>& grp, const Finish& finish, const Begin& begin) {
+  for (auto& G : grp) begin(G);
+  auto any_in_flight = [&]() {
+    for (const auto& G : grp)
+      if (G.in_flight) return true;
+    return false;
+  };
+  for (size_t g = 0; any_in_flight(); g = (g + 1) % grp.size()) {
+    if (!grp[g].in_flight) continue;
+    finish(grp[g]);
+    begin(grp[g]);
+  }
+}
 
 // Round overlap pays where the drain after each Nelder-Mead round is a large part of the round:
 // one 8-way shard of the north job (8 outputs per call, two groups of 4) 2.70 -> 2.45 s per step.
@@ -167,14 +246,19 @@ struct OverlapGroup {
 constexpr int kOverlapMaxOutputs = 16;
 constexpr int kOverlapGroupAuto = 8;
 
-using AcceptFn = std::function<void(int, double, const double*, const double*, int64_t)>;
+struct OverlapGroup : RoundGroup {
+  double *alpha_all = nullptr, *asend_all = nullptr, *dout = nullptr;
+};
+struct StagingScope {   // h2d through group g's pinned arena inside the scope
+  gpar_ctx* c;
+  StagingScope(gpar_ctx* c_, int g) : c(c_) { c->staging = &c->stage[g]; }
+  ~StagingScope() { c->staging = nullptr; }
+};
 
-static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
-                           std::vector<NelderMead>& nm, const AcceptFn& accept) {
+// fit_overlapped's groups with their events, workspaces ("ov*g<k>") and arenas
+static std::vector<OverlapGroup> overlap_groups(gpar_ctx* c, const std::vector<DevProblem>& P) {
   const int np = (int)P.size();
-  const int64_t n = P[0].n, nch = P[0].nch, npart = vec_fix_blocks(n);
-  int64_t mpmax = 0;
-  for (auto& p : P) mpmax = std::max(mpmax, p.mp);
+  const int64_t n = P[0].n, nch = P[0].nch, npart = vec_fix_blocks(n), mpmax = max_mp(P);
   const size_t sq = (size_t)mpmax * mpmax;
   // K groups of about overlap_group outputs (at least two), dealt round-robin
   const int gs = c->overlap_group > 0 ? c->overlap_group : kOverlapGroupAuto;
@@ -185,14 +269,10 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
       HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       evs->push_back(ev);
     }
-  if ((int)c->stage.size() < K) c->stage.resize(K);   // no arena is in use between calls
-  std::vector<OverlapGroup> grp(K);
-  for (int i = 0; i < np; ++i) grp[i % K].members.push_back(i);
-  for (int g = 0; g < K; ++g) {
-    OverlapGroup& G = grp[g];
-    G.id = g;
+  std::vector<OverlapGroup> grp = deal_groups<OverlapGroup>(np, K);
+  for (OverlapGroup& G : grp) {
     const size_t cap = G.members.size();
-    const std::string sfx = "g" + std::to_string(g);
+    const std::string sfx = "g" + std::to_string(G.id);
     G.go.ldg = mpmax;
     G.go.npart = npart;
     G.go.G = ws<double>(c, "ovG" + sfx, cap * sq);
@@ -202,27 +282,18 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
     G.alpha_all = ws<double>(c, "ovalpha" + sfx, cap * n);
     G.asend_all = ws<double>(c, "ovasend" + sfx, cap * nch * kSStride);
     G.dout = ws<double>(c, "ovout" + sfx, cap);
-    gpar_ctx::Staging& s = c->stage[g];
-    const size_t vbytes = (cap * sizeof(double) + 255) & ~(size_t)255;
-    G.res_bytes = vbytes + ((2 * cap * sizeof(int) + 255) & ~(size_t)255);
-    const size_t need = G.res_bytes + ((size_t)1 << 20) + cap * 4096;
-    if (s.cap < need) {
-      if (s.host) HIPCHECK(hipHostFree(s.host));
-      s.host = nullptr;
-      s.cap = 0;
-      HIPCHECK(hipHostMalloc((void**)&s.host, need, hipHostMallocDefault));
-      s.cap = need;
-    }
-    G.hout = reinterpret_cast<double*>(s.host);
-    G.hstat = reinterpret_cast<int*>(s.host + vbytes);
+    group_result_arena(c, G);
   }
-  reserve_gram_parts(c, P, 1);
-  struct StagingScope {   // h2d through group g's pinned arena inside the scope
-    gpar_ctx* c;
-    StagingScope(gpar_ctx* c_, int g) : c(c_) { c->staging = &c->stage[g]; }
-    ~StagingScope() { c->staging = nullptr; }
-  };
+  return grp;
+}
 
+static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
+                           std::vector<NelderMead>& nm, const AcceptFn& accept) {
+  const int np = (int)P.size();
+  const int64_t n = P[0].n, nch = P[0].nch, npart = vec_fix_blocks(n), mpmax = max_mp(P);
+  const size_t sq = (size_t)mpmax * mpmax;
+  std::vector<OverlapGroup> grp = overlap_groups(c, P);
+  reserve_gram_parts(c, P, 1);
   // compact gains records (compact_rec -1 = auto) when every output already whitens through
   // whiten_kfu_d2x2 (cached distances, or inputs wider than the fused kernels take): an uncached
   // narrow output would otherwise switch from the fused whitening to the distance pass (last bits)
@@ -259,25 +330,14 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
   };
   // ask every active member for its next point; queue the group's gains and its jobs
   auto begin_round = [&](OverlapGroup& G) {
-    G.act.clear();
-    for (int i : G.members)
-      if (!nm[i].done()) G.act.push_back(i);
-    if (G.act.empty()) return;
+    if (!ask_group(c, G, nm, P)) return;
     const int na = (int)G.act.size();
-    G.th.clear();
-    G.sub.clear();
     std::vector<ChainParamsHost> cps(na);
     std::vector<const double*> ys(na);
     for (int a = 0; a < na; ++a) {
-      const int i = G.act[a];
-      const auto& x = nm[i].ask();
-      G.th.push_back({unpack(x[0]), unpack(x[1]), unpack(x[2]), unpack(x[3]), unpack(x[4])});
-      G.sub.push_back(P[i]);
-      const Theta& t = G.th.back();
-      cps[a] = {1.0 / t.l_t, t.l_t, t.sv_t * t.sv_t, t.sigma * t.sigma};
-      ys[a] = P[i].y;
+      cps[a] = chain_params_of(G.th[a]);
+      ys[a] = G.sub[a].y;
     }
-    c->stage[G.id].used = G.res_bytes;   // the previous round's uploads have been consumed
     // compact records (auto): the gains beside the other group's whitenings write 72 instead of
     // 168 bytes per step, the 8-output shard 2.329 -> 2.296 s per step (r04w)
     // the gains run on the whitening CUs beside the other group's whitenings (s_d), not in the
@@ -306,11 +366,7 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
       StageJob j;
       j.p = &G.sub[a];
       j.th = &G.th[a];
-      j.gi = gn;
-      j.gi.rec = gn.rec + (size_t)a * gn.recstride;
-      j.gi.g = gn.g + (size_t)a * gn.gstride;
-      j.gi.phi = gn.phi + (size_t)a * gn.phistride;
-      j.gi.logs = gn.logs + (size_t)a * nch;
+      j.gi = slice_gains(gn, a, nch);
       j.alpha = G.alpha_all + (size_t)a * n;
       j.asend = G.asend_all + (size_t)a * nch * kSStride;
       j.G = G.go.G + a * sq;
@@ -329,26 +385,11 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
     if (sp.has_pending && sp.pending.group == G.id) sp.flush();   // its last Gram, then its tail
     HIPCHECK(hipEventSynchronize(c->ev_grp[G.id]));
     OnStream on_(c, c->s_g);
-    for (size_t a = 0; a < G.act.size(); ++a) {
-      double f = -G.hout[a];
-      if (G.hstat[2 * a] || G.hstat[2 * a + 1] || !std::isfinite(f)) f = INFINITY;
-      accept(G.act[a], f, G.go.G + a * sq, G.go.r + a * mpmax, mpmax);
-    }
-    G.in_flight = false;
+    tell_group(G, accept);
   };
   sp.start();
   HIPCHECK(hipStreamWaitEvent(c->s_d, c->ev_sp, 0));   // the inputs / distance cache on main
-  for (auto& G : grp) begin_round(G);
-  auto any_in_flight = [&]() {
-    for (const auto& G : grp)
-      if (G.in_flight) return true;
-    return false;
-  };
-  for (int g = 0; any_in_flight(); g = (g + 1) % K) {
-    if (!grp[g].in_flight) continue;
-    finish_round(grp[g]);
-    begin_round(grp[g]);
-  }
+  run_groups(grp, finish_round, begin_round);
   sp.flush();
   sp.join(c->main);
 }
@@ -380,23 +421,13 @@ constexpr int64_t kOverlapUnsplitMinMp = 512;
 
 static void fit_overlapped_unsplit(gpar_ctx* c, const std::vector<DevProblem>& P,
                                    std::vector<NelderMead>& nm, const AcceptFn& accept) {
+  struct UGroup : RoundGroup {
+    hipStream_t st[3] = {nullptr, nullptr, nullptr};   // main, side, dense
+    hipEvent_t done = nullptr;
+  };
   const int np = (int)P.size();
   const int K = c->overlap_group > 0 ? std::max(2, (np + c->overlap_group - 1) / c->overlap_group) : 2;
-  struct UGroup {
-    int id = 0;
-    std::vector<int> members, act;
-    std::vector<Theta> th;
-    std::vector<DevProblem> sub;
-    GramOut go{};
-    hipStream_t st[3] = {nullptr, nullptr, nullptr};   // main, side, dense
-    double* hout = nullptr;
-    int* hstat = nullptr;
-    hipEvent_t done = nullptr;
-    size_t res_bytes = 0;
-    bool in_flight = false;
-  };
-  std::vector<UGroup> grp(K);
-  for (int i = 0; i < np; ++i) grp[i % K].members.push_back(i);
+  std::vector<UGroup> grp = deal_groups<UGroup>(np, K);
   // streams and events made here are released on every exit, after their work
   struct Owned {
     std::vector<hipStream_t> st;
@@ -416,12 +447,9 @@ static void fit_overlapped_unsplit(gpar_ctx* c, const std::vector<DevProblem>& P
     own.st.push_back(s);
     return s;
   };
-  if ((int)c->stage.size() < K) c->stage.resize(K);   // no arena is in use between calls
   HIPCHECK(hipEventRecord(c->ev_fork, c->main));   // the inputs and the distance cache, on main
-  for (int g = 0; g < K; ++g) {
-    UGroup& G = grp[g];
-    G.id = g;
-    if (g == 0) {
+  for (UGroup& G : grp) {
+    if (G.id == 0) {
       G.st[0] = c->main;
       G.st[1] = c->side;
       G.st[2] = c->s_d;
@@ -433,20 +461,7 @@ static void fit_overlapped_unsplit(gpar_ctx* c, const std::vector<DevProblem>& P
     }
     HIPCHECK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
     own.ev.push_back(G.done);
-    const size_t cap = G.members.size();
-    gpar_ctx::Staging& a = c->stage[g];
-    const size_t vbytes = (cap * sizeof(double) + 255) & ~(size_t)255;
-    G.res_bytes = vbytes + ((2 * cap * sizeof(int) + 255) & ~(size_t)255);
-    const size_t need = G.res_bytes + ((size_t)1 << 20) + cap * 4096;
-    if (a.cap < need) {
-      if (a.host) HIPCHECK(hipHostFree(a.host));
-      a.host = nullptr;
-      a.cap = 0;
-      HIPCHECK(hipHostMalloc((void**)&a.host, need, hipHostMallocDefault));
-      a.cap = need;
-    }
-    G.hout = reinterpret_cast<double*>(a.host);
-    G.hstat = reinterpret_cast<int*>(a.host + vbytes);
+    group_result_arena(c, G);
   }
   // a group's streams, workspaces and upload arena, for the scope of its launches
   struct GroupScope {
@@ -474,19 +489,9 @@ static void fit_overlapped_unsplit(gpar_ctx* c, const std::vector<DevProblem>& P
       c->staging = nullptr;
     }
   };
+  // a round is one eval_dtc on the group's streams, returning as soon as it is queued
   auto issue = [&](UGroup& G) {
-    G.act.clear();
-    for (int i : G.members)
-      if (!nm[i].done()) G.act.push_back(i);
-    if (G.act.empty()) return;
-    G.th.clear();
-    G.sub.clear();
-    for (int i : G.act) {
-      const auto& x = nm[i].ask();
-      G.th.push_back({unpack(x[0]), unpack(x[1]), unpack(x[2]), unpack(x[3]), unpack(x[4])});
-      G.sub.push_back(P[i]);
-    }
-    c->stage[G.id].used = G.res_bytes;   // the previous round's uploads have been consumed
+    if (!ask_group(c, G, nm, P)) return;
     GroupScope gs_(c, G);
     const EvalAsync as{G.hout, G.hstat, G.done};
     std::vector<int> unused;
@@ -496,25 +501,9 @@ static void fit_overlapped_unsplit(gpar_ctx* c, const std::vector<DevProblem>& P
   auto finish = [&](UGroup& G) {
     HIPCHECK(hipEventSynchronize(G.done));
     OnStream on_(c, G.st[0]);   // a kept point's Gram copy, ahead of the group's next round
-    const size_t sq = (size_t)G.go.ldg * G.go.ldg;
-    for (size_t a = 0; a < G.act.size(); ++a) {
-      double f = -G.hout[a];
-      if (G.hstat[2 * a] || G.hstat[2 * a + 1] || !std::isfinite(f)) f = INFINITY;
-      accept(G.act[a], f, G.go.G + a * sq, G.go.r + a * G.go.ldg, G.go.ldg);
-    }
-    G.in_flight = false;
+    tell_group(G, accept);
   };
-  for (auto& G : grp) issue(G);
-  auto any_in_flight = [&]() {
-    for (const auto& G : grp)
-      if (G.in_flight) return true;
-    return false;
-  };
-  for (int g = 0; any_in_flight(); g = (g + 1) % K) {
-    if (!grp[g].in_flight) continue;
-    finish(grp[g]);
-    issue(grp[g]);
-  }
+  run_groups(grp, finish, issue);
   // the context's stream follows every group's work (kept Grams, the streams released above)
   for (int g = 1; g < K; ++g)
     for (hipStream_t s : grp[g].st)
@@ -549,7 +538,7 @@ static std::vector<std::vector<int>> cache_chunks(gpar_ctx* c, const std::vector
     }
     return out;
   }
-  if (fit_pipelined(c, P)) return out;
+  if (stage_plan(c, P).pipelined) return out;
   std::vector<int> narrow, wide;
   for (int i = 0; i < np; ++i) (P[i].d >= kDistCacheMinD ? wide : narrow).push_back(i);
   if (wide.size() < 2) return out;
@@ -590,61 +579,65 @@ static std::vector<std::vector<int>> cache_chunks(gpar_ctx* c, const std::vector
   return out;
 }
 
+// the distance cache is dropped here unless the caller keeps it (gpar_ctx_set_dist_cache_keep)
+struct CacheRelease {
+  gpar_ctx* c;
+  ~CacheRelease() {
+    if (c->dist_cache_keep) return;
+    try {
+      release_dist_cache(c);
+    } catch (...) {
+    }
+  }
+};
+
+// The fit in cache_chunks' sub-batches: each is one batch, and the cache buffers pass from one
+// sub-batch to the next (re-allocating tens of GB per sub-batch costs seconds: fresh VRAM is
+// cleared); released at the end unless the caller keeps them.
+static void fit_in_chunks(gpar_ctx* ctx, const std::vector<DevProblem>& P0,
+                          const std::vector<std::vector<int>>& chunks, const double* log_theta0,
+                          const gpar_fit_options& o, double* theta_out, double* nlml_out,
+                          int32_t* evals_out, int64_t later_bytes) {
+  struct Restore {
+    gpar_ctx* c;
+    int chunks;
+    bool keep;
+    ~Restore() {
+      c->fit_chunks = chunks;
+      c->dist_cache_keep = keep;
+      CacheRelease release_{c};
+    }
+  } restore_{ctx, ctx->fit_chunks, ctx->dist_cache_keep};
+  ctx->fit_chunks = 0;
+  ctx->dist_cache_keep = true;
+  for (const auto& idx : chunks) {
+    const size_t k = idx.size();
+    std::vector<DevProblem> sub;
+    std::vector<double> x0(5 * k), th(5 * k), nl(k);
+    std::vector<int32_t> ev(k);
+    for (size_t a = 0; a < k; ++a) {
+      sub.push_back(P0[idx[a]]);
+      std::copy(log_theta0 + 5 * idx[a], log_theta0 + 5 * idx[a] + 5, x0.begin() + 5 * a);
+    }
+    fit_impl(ctx, sub, x0.data(), o, th.data(), nl.data(), ev.data(), nullptr, later_bytes);
+    for (size_t a = 0; a < k; ++a) {
+      std::copy(th.begin() + 5 * a, th.begin() + 5 * a + 5, theta_out + 5 * idx[a]);
+      if (nlml_out) nlml_out[idx[a]] = nl[a];
+      if (evals_out) evals_out[idx[a]] = ev[a];
+    }
+  }
+}
+
 void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* log_theta0,
                      const gpar_fit_options& o, double* theta_out, double* nlml_out,
                      int32_t* evals_out, FitKeep* keep, int64_t later_bytes) {
   if (!keep) {   // (the kept Grams are named by batch index: one batch when they are wanted)
     const std::vector<std::vector<int>> chunks = cache_chunks(ctx, P0, later_bytes);
-    if (!chunks.empty()) {
-      // each sub-batch is one batch, and the cache buffers pass from one sub-batch to the next
-      // (re-allocating tens of GB per sub-batch costs seconds: fresh VRAM is cleared); released at
-      // the end unless the caller keeps them
-      struct Restore {
-        gpar_ctx* c;
-        int chunks;
-        bool keep;
-        ~Restore() {
-          c->fit_chunks = chunks;
-          c->dist_cache_keep = keep;
-          if (keep) return;
-          try {
-            release_dist_cache(c);
-          } catch (...) {
-          }
-        }
-      } restore_{ctx, ctx->fit_chunks, ctx->dist_cache_keep};
-      ctx->fit_chunks = 0;
-      ctx->dist_cache_keep = true;
-      for (const auto& idx : chunks) {
-        const size_t k = idx.size();
-        std::vector<DevProblem> sub;
-        std::vector<double> x0(5 * k), th(5 * k), nl(k);
-        std::vector<int32_t> ev(k);
-        for (size_t a = 0; a < k; ++a) {
-          sub.push_back(P0[idx[a]]);
-          std::copy(log_theta0 + 5 * idx[a], log_theta0 + 5 * idx[a] + 5, x0.begin() + 5 * a);
-        }
-        fit_impl(ctx, sub, x0.data(), o, th.data(), nl.data(), ev.data(), nullptr, later_bytes);
-        for (size_t a = 0; a < k; ++a) {
-          std::copy(th.begin() + 5 * a, th.begin() + 5 * a + 5, theta_out + 5 * idx[a]);
-          if (nlml_out) nlml_out[idx[a]] = nl[a];
-          if (evals_out) evals_out[idx[a]] = ev[a];
-        }
-      }
-      return;
-    }
+    if (!chunks.empty())
+      return fit_in_chunks(ctx, P0, chunks, log_theta0, o, theta_out, nlml_out, evals_out,
+                           later_bytes);
   }
-  // the cache lives for this fit call only, unless the caller keeps it (gpar_ctx_set_dist_cache_keep)
-  struct CacheRelease {
-    gpar_ctx* c;
-    ~CacheRelease() {
-      if (c->dist_cache_keep) return;
-      try {
-        release_dist_cache(c);
-      } catch (...) {
-      }
-    }
-  } release_{ctx};
+  CacheRelease release_{ctx};   // the cache lives for this fit call only
   const std::vector<DevProblem> P =
       attach_dist_cache(ctx, P0, fit_ws_estimate(ctx, P0) + later_bytes);
   const int nprob = (int)P.size();
@@ -680,17 +673,15 @@ void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* lo
     }
     nm[i].tell(f);
   };
-  int64_t mpmax = 0;
-  for (auto& p : P) mpmax = std::max(mpmax, p.mp);
-  if (ctx->overlap && nprob >= 4 && (nprob <= kOverlapMaxOutputs || ctx->overlap_group > 0) &&
-      fit_pipelined(ctx, P) &&
-      split_active(ctx, P[0].n, mpmax))
+  // the round overlaps, on the schedule the rounds themselves would take: the CU-split pipeline,
+  // or unsplit rounds that run the grouped Gram
+  const StagePlan sp = stage_plan(ctx, P);
+  const bool many = ctx->overlap && nprob >= 4;
+  if (many && sp.split && (nprob <= kOverlapMaxOutputs || ctx->overlap_group > 0))
     fit_overlapped(ctx, P, nm, accept);
-  else if (ctx->overlap && nprob >= 4 &&
-           ((nprob <= kOverlapUnsplitMax && mpmax >= kOverlapUnsplitMinMp) ||
-            ctx->overlap_group > 0) &&
-           fit_pipelined(ctx, P) && !split_active(ctx, P[0].n, mpmax) &&
-           grouped_gram_eligible(ctx, P))
+  else if (many && sp.pipelined && !sp.split && sp.gram_group >= 2 &&
+           ((nprob <= kOverlapUnsplitMax && sp.mpmax >= kOverlapUnsplitMinMp) ||
+            ctx->overlap_group > 0))
     fit_overlapped_unsplit(ctx, P, nm, accept);
   std::vector<double> vals;
   while (true) {
@@ -702,17 +693,14 @@ void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* lo
     std::vector<Theta> th;
     for (int i : act) {
       sub.push_back(P[i]);
-      const auto& x = nm[i].ask();
-      th.push_back({unpack(x[0]), unpack(x[1]), unpack(x[2]), unpack(x[3]), unpack(x[4])});
+      th.push_back(theta_of(nm[i].ask()));
     }
     vals.assign(act.size(), 0.0);
     std::vector<int> st;
     GramOut go{};
     eval_dtc(ctx, sub, th, vals.data(), st, keep ? &go : nullptr);
     for (size_t a = 0; a < act.size(); ++a) {
-      double f = -vals[a];
-      if (st[a] || !std::isfinite(f)) f = INFINITY;  // PosDefException -> reject the point
-      accept(act[a], f, keep ? go.G + a * go.ldg * go.ldg : nullptr,
+      accept(act[a], told_value(vals[a], st[a] != 0), keep ? go.G + a * go.ldg * go.ldg : nullptr,
              keep ? go.r + a * go.ldg : nullptr, go.ldg);
     }
   }

@@ -4,7 +4,6 @@
 
 namespace gpar {
 
-
 // Kfu assembly + chunk-local whitening: fp64-MFMA Gram-form kernel for the smooth output
 // kernels, direct-difference kernel for Matern-1/2 (kappa not smooth in d^2 at 0).
 // Inputs wider than kFusedMaxD (the fused kernels keep a column's pseudo-input in registers):
@@ -36,28 +35,12 @@ void whiten_kfu_any(gpar_ctx* c, const DevProblem& p, const GainsOut& gi, const 
   }
 }
 
-StageBufs stage_bufs(gpar_ctx* c, int l, int64_t n, int64_t mpmax) {
+// Stage buffers under workspace names ending in sfx; idx: the stream lane (carry tags).
+static StageBufs stage_bufs_named(gpar_ctx* c, int idx, const std::string& sfx, int64_t n,
+                                  int64_t mpmax, double* send = nullptr, double* cin = nullptr) {
   const int64_t nch = (n + kChunk - 1) / kChunk;
-  const std::string sfx = l ? "_1" : "";
   StageBufs b;
-  b.idx = l;
-  b.beta = ws<double>(c, "beta" + sfx, (size_t)(n + 16) * mpmax);
-  b.alpha = ws<double>(c, "alpha" + sfx, (size_t)n);
-  b.send = ws<double>(c, "send" + sfx, (size_t)nch * (mpmax + 1) * 4);
-  b.cin = ws<double>(c, "cin" + sfx, (size_t)nch * (mpmax + 1) * 4);
-  b.hsum = ws<double>(c, "hsum" + sfx, (size_t)nch * (mpmax + 1) * 4);
-  b.qv = ws<double>(c, "qv" + sfx, (size_t)nch * 4);
-  return b;
-}
-
-// The grouped Gram's per-output stage buffers: slot `slot` of a group, carry tags of stream lane
-// `lane` (its carry workspaces are reused output after output on that lane).
-static StageBufs stage_bufs_grp(gpar_ctx* c, int lane, int slot, int64_t n, int64_t mpmax,
-                                double* send = nullptr, double* cin = nullptr) {
-  const int64_t nch = (n + kChunk - 1) / kChunk;
-  const std::string sfx = "_g" + std::to_string(slot);
-  StageBufs b;
-  b.idx = lane;
+  b.idx = idx;
   b.beta = ws<double>(c, "beta" + sfx, (size_t)(n + 16) * mpmax);
   b.alpha = ws<double>(c, "alpha" + sfx, (size_t)n);
   // the carry's input / output: the group's shared arrays when its carries run batched
@@ -66,6 +49,9 @@ static StageBufs stage_bufs_grp(gpar_ctx* c, int lane, int slot, int64_t n, int6
   b.hsum = ws<double>(c, "hsum" + sfx, (size_t)nch * (mpmax + 1) * 4);
   b.qv = ws<double>(c, "qv" + sfx, (size_t)nch * 4);
   return b;
+}
+StageBufs stage_bufs(gpar_ctx* c, int l, int64_t n, int64_t mpmax) {
+  return stage_bufs_named(c, l, l ? "_1" : "", n, mpmax);
 }
 
 // Outputs per grouped Gram launch set (0: per-output Grams).  Small problems only: one output's
@@ -79,10 +65,11 @@ constexpr double kGramGroupMaxWork = 5e10;
 constexpr int kGramGroupAuto = 8;
 constexpr int64_t kGramGroupMaxBytes = (int64_t)24 << 30;   // the group's beta buffers
 constexpr int64_t kGrpMinRows = 4096;   // rows per OFF workgroup below which the share stays 1/cnt
-static int gram_group_size(gpar_ctx* c, const std::vector<DevProblem>& P, int64_t n,
-                           int64_t mpmax, bool fix_beta, int nlanes, bool split_pipe) {
+static int gram_group_size(const gpar_ctx* c, const std::vector<DevProblem>& P,
+                           const StagePlan& sp, bool fix_beta) {
   const int np = (int)P.size();
-  if (fix_beta || nlanes > 1 || split_pipe || np < 2) return 0;
+  const int64_t n = P[0].n, mpmax = sp.mpmax;
+  if (fix_beta || sp.nlanes > 1 || sp.split || np < 2) return 0;
   // the grouped launch takes one chunk-correction template (sdim) and carry stride (mc) for the
   // whole group: outputs with another time kernel keep the per-output Grams
   for (const auto& p : P)
@@ -99,11 +86,24 @@ static int gram_group_size(gpar_ctx* c, const std::vector<DevProblem>& P, int64_
   return g >= 2 ? g : 0;
 }
 
-// an unsplit batched round of these problems would run the grouped Gram
-bool grouped_gram_eligible(gpar_ctx* c, const std::vector<DevProblem>& P) {
-  int64_t mpmax = 0;
-  for (const auto& p : P) mpmax = std::max(mpmax, p.mp);
-  return gram_group_size(c, P, P[0].n, mpmax, false, 1, false) >= 2;
+StagePlan stage_plan(const gpar_ctx* c, const std::vector<DevProblem>& P, bool fix_beta) {
+  StagePlan sp;
+  sp.mpmax = max_mp(P);
+  sp.shared = shares_grid(P);
+  sp.pipelined = fit_pipelined(c, P, fix_beta);
+  sp.split = sp.pipelined && split_active(c, P[0].n, sp.mpmax);
+  sp.nlanes = (P.size() > 1 && !fix_beta && c->lanes > 1) ? 2 : 1;
+  sp.gram_group = gram_group_size(c, P, sp, fix_beta);
+  return sp;
+}
+
+// The stage's first Gram launch waits on its stream (c->stream), immediately ahead of the launch,
+// for the round's dense prefix when eval_dtc runs it on s_d (beside a Gram the latency-bound
+// 64 x 64 launches slowed it 4.4 -> 5.3 ms at the eeg shard), and empties the slot for the rest.
+static void wait_dense_prefix(gpar_ctx* c, hipEvent_t* after) {
+  if (!after || !*after) return;
+  HIPCHECK(hipStreamWaitEvent(c->stream, *after, 0));
+  *after = nullptr;
 }
 
 // Kfu assembly + chunk-local whitening of j's output into b.beta, on c->stream.
@@ -174,10 +174,7 @@ void stage_gram(gpar_ctx* c, const StageJob& j, const StageBufs& b, bool fix_bet
                        bool one_per_cu, const std::string& part_sfx, hipStream_t side, int cus,
                        hipStream_t st_w, hipEvent_t ev_w, int w_frac32, int dg_rows_w) {
   const DevProblem& p = *j.p;
-  if (c->gram_after) {   // the round's dense prefix (eval_dtc) first
-    HIPCHECK(hipStreamWaitEvent(c->stream, c->gram_after, 0));
-    c->gram_after = nullptr;
-  }
+  wait_dense_prefix(c, j.after);
   GramPlan plan = gram_plan(p.n, p.mp, one_per_cu, cus, st_w ? 256 : cus);
   const int w_items = st_w ? plan.ndg * plan.sdg * w_frac32 / 32 : 0;
   // dg_rows_w: the DG time splits that run on the whitening CUs take that many percent more rows
@@ -232,269 +229,282 @@ void reserve_gram_parts(gpar_ctx* c, const std::vector<DevProblem>& P, int nlane
 //   Gram is a plain beta^T beta.  One extra pass over beta, but G carries the rounding of the
 //   true beta only: q(u) factors the noise-free Cuu (cond >= 1e7), which amplifies the ~10x
 //   larger rounding of the correction form (emulated: 7e-15 vs 7e-16 of max |G|).
-GramOut run_gram_stage(gpar_ctx* c, const std::vector<DevProblem>& P,
-                              const std::vector<Theta>& th, bool fix_beta) {
-  const int np = (int)P.size();
-  int64_t mpmax = 0, n = P[0].n;
-  for (auto& p : P) mpmax = std::max(mpmax, p.mp);
-  const int64_t nch = (n + kChunk - 1) / kChunk;
-  const int64_t npart = vec_fix_blocks(n);
-  GramOut o;
-  o.ldg = mpmax;
-  o.npart = npart;
-  o.G = ws<double>(c, "G", (size_t)np * mpmax * mpmax);
-  o.r = ws<double>(c, "r", (size_t)np * mpmax);
-  o.a2part = ws<double>(c, "a2part", (size_t)np * npart);
-  o.logs = ws<double>(c, "logs_all", (size_t)np * nch);
-  // problems narrower than the batch's widest: their G / r padding must read as zero in the
-  // dense tail (the Gram writes only the mp x mp corner)
-  for (int i = 0; i < np; ++i)
-    if (P[i].mp != mpmax) {
-      HIPCHECK(hipMemsetAsync(o.G + (size_t)i * mpmax * mpmax, 0, (size_t)mpmax * mpmax * sizeof(double), c->stream));
-      HIPCHECK(hipMemsetAsync(o.r + (size_t)i * mpmax, 0, (size_t)mpmax * sizeof(double), c->stream));
-    }
-
-  // group problems sharing (t, n, time kernel) into one batched gains launch
-  const bool shared = shares_grid(P);
-  const bool pipe = fit_pipelined(c, P, fix_beta);
-  const bool split_pipe = pipe && split_active(c, n, mpmax);
-  // a split round's head: the first output's gains on the whitening CUs and the others' beside
-  // them on the Gram CUs (r04j; the variants tried in r04 -- every gains first, whole-chip or not;
-  // the first job on the Gram CUs; the late gains beside the Grams -- measured slower)
-  const bool split_head = split_pipe && shared && np > 1;
-  const double* logs_src = nullptr;
-  std::vector<GainsOut> gains(np);
-  GainsPlan gplan;
+//
+// What the stage's four schedules share: the outputs' G / r / partial-sum slots, the shared-gains
+// plan (problems sharing (t, n, time kernel) take one batched gains launch) and the per-output
+// stage jobs.  The schedules below hold only their own ordering of the launches.
+struct GramStage {
+  gpar_ctx* c;
+  const std::vector<DevProblem>& P;
+  const std::vector<Theta>& th;
+  const bool fix_beta;
+  const StagePlan sp;
+  const int np;
+  const int64_t n, nch, npart, mpmax;
+  GramOut o{};
   // shared gains: every output's alpha_loc (y filtered from zero per chunk) comes out of the
   // gains pass itself; only its chunk end states are copied into the carry's alpha column
-  double* alpha_all = nullptr;
-  double* asend_all = nullptr;
-  if (shared) {
+  GainsPlan gplan{};
+  double *alpha_all = nullptr, *asend_all = nullptr;
+  std::vector<StageJob> jobs;
+  hipEvent_t after;   // the round's dense prefix, until the first Gram takes it (wait_dense_prefix)
+
+  GramStage(gpar_ctx* c_, const std::vector<DevProblem>& P_, const std::vector<Theta>& th_,
+            bool fix_beta_, hipEvent_t after_)
+      : c(c_), P(P_), th(th_), fix_beta(fix_beta_), sp(stage_plan(c_, P_, fix_beta_)),
+        np((int)P_.size()), n(P_[0].n), nch((n + kChunk - 1) / kChunk), npart(vec_fix_blocks(n)),
+        mpmax(sp.mpmax), jobs(np), after(after_) {
+    o.ldg = mpmax;
+    o.npart = npart;
+    o.G = ws<double>(c, "G", (size_t)np * mpmax * mpmax);
+    o.r = ws<double>(c, "r", (size_t)np * mpmax);
+    o.a2part = ws<double>(c, "a2part", (size_t)np * npart);
+    o.logs = ws<double>(c, "logs_all", (size_t)np * nch);
+    // problems narrower than the batch's widest: their G / r padding must read as zero in the
+    // dense tail (the Gram writes only the mp x mp corner)
+    for (int i = 0; i < np; ++i)
+      if (P[i].mp != mpmax) {
+        HIPCHECK(hipMemsetAsync(o.G + (size_t)i * mpmax * mpmax, 0, (size_t)mpmax * mpmax * sizeof(double), c->stream));
+        HIPCHECK(hipMemsetAsync(o.r + (size_t)i * mpmax, 0, (size_t)mpmax * sizeof(double), c->stream));
+      }
+    if (sp.shared) plan_shared_gains();
+    reserve_gram_parts(c, P, sp.nlanes);
+  }
+
+  // Every schedule but the split pipeline runs the batched gains here, on the caller's stream;
+  // gram_stage_split launches them itself, over its own streams.
+  void plan_shared_gains() {
     std::vector<ChainParamsHost> cps(np);
     std::vector<const double*> ys(np);
     for (int i = 0; i < np; ++i) {
-      cps[i] = {1.0 / th[i].l_t, th[i].l_t, th[i].sv_t * th[i].sv_t, th[i].sigma * th[i].sigma};
+      cps[i] = chain_params_of(th[i]);
       ys[i] = P[i].y;
     }
     alpha_all = ws<double>(c, "alpha_all", (size_t)np * n);
     asend_all = ws<double>(c, "asend_all", (size_t)np * nch * kSStride);
-    // split pipeline (split_head): the first output's gains on the whitening CUs, ahead of its
-    // whitening there, and the others' at the same time on the Gram CUs, ahead of the first Gram;
-    // the second whitening waits for them (below).  Tried: the first whitening whole-chip, beside
-    // the others' gains (head 8.6 ms per round, r04f) or ahead of them (they then delayed the
-    // second whitening and every Gram after it, r04i); the others' gains in groups on the
-    // whitening stream (they delayed the Grams' DG share: 5.10 -> 5.24 ms per Gram, r04h).
     // compact records (split pipeline only: its every whitening is whiten_kfu_d2x2) when asked:
     // in the round-by-round fit they made the round head's first whitening slower beside the
     // other outputs' (now faster) gains, 5.6 -> 8.6 ms per round, 17.77 -> 17.91 s per job (r04x)
     gplan = plan_gains(c, P[0].sdim, P[0].t, n, cps, nullptr, false, "fit", &ys, alpha_all,
-                       asend_all, /*compact=*/split_pipe && c->compact_rec == 1);
-    if (!split_head) gplan.launch(c->stream, 0, np);
-    const GainsOut& g = gplan.o;
-    for (int i = 0; i < np; ++i) {
-      gains[i] = g;
-      gains[i].rec = g.rec + (size_t)i * g.recstride;
-      gains[i].g = g.g + (size_t)i * g.gstride;
-      gains[i].phi = g.phi + (size_t)i * g.phistride;
-      gains[i].logs = g.logs + (size_t)i * nch;
-    }
-    if (!split_head)   // else after the pipeline (later groups' gains run on the whitening stream)
-      HIPCHECK(hipMemcpyAsync(o.logs, g.logs, (size_t)np * nch * sizeof(double),
-                              hipMemcpyDeviceToDevice, c->stream));
-    logs_src = g.logs;
+                       asend_all, /*compact=*/sp.split && c->compact_rec == 1);
+    if (sp.split) return;
+    gplan.launch(c->stream, 0, np);
+    copy_shared_logs();
+  }
+  void copy_shared_logs() {
+    HIPCHECK(hipMemcpyAsync(o.logs, gplan.o.logs, (size_t)np * nch * sizeof(double),
+                            hipMemcpyDeviceToDevice, c->stream));
   }
 
-  // Outputs alternate between the context stream and a side stream, each with its own
-  // beta / alpha / carry workspace, so one output's (VALU-bound) whitening overlaps another's
-  // (MFMA-bound) Gram.  Gains are shared: the side stream waits for them (fork event).
-  const int nlanes = (np > 1 && !fix_beta && c->lanes > 1) ? 2 : 1;
-  // One lane, pipelined (the batched fit): the big kernels stay in order on the context stream,
-  // whitening(i + 1) issued ahead of Gram(i), and output i's short chain between them (alpha's end
-  // states, the chunk carry, vec_fix, the beta tail) runs on the side stream beside a whitening
-  // instead of on the critical path.  Two beta / carry buffers (fit_pipelined).
-  reserve_gram_parts(c, P, nlanes);
-  // the stage job of output i, its gains (per output unless shared) run on c->stream
-  std::vector<StageJob> jobs(np);
-  std::vector<double*> alpha_own(np, nullptr);
-  auto job = [&](int i, const StageBufs& b) -> const StageJob& {
+  // the stage job of output i; its gains (per output unless shared) run on c->stream
+  const StageJob& job(int i, const StageBufs& b) {
     StageJob& j = jobs[i];
     j.p = &P[i];
     j.th = &th[i];
-    if (shared) {
-      j.gi = gains[i];
+    if (sp.shared) {
+      j.gi = slice_gains(gplan.o, i, nch);
       j.alpha = alpha_all + (size_t)i * n;
       j.asend = asend_all + (size_t)i * nch * kSStride;
     } else {
-      std::vector<ChainParamsHost> cps(1);
-      cps[0] = {1.0 / th[i].l_t, th[i].l_t, th[i].sv_t * th[i].sv_t, th[i].sigma * th[i].sigma};
+      const std::vector<ChainParamsHost> cps{chain_params_of(th[i])};
       j.gi = run_gains(c, P[i].sdim, P[i].t, n, cps, nullptr, false, b.idx ? "fit1_1" : "fit1");
       HIPCHECK(hipMemcpyAsync(o.logs + (size_t)i * nch, j.gi.logs, nch * sizeof(double),
                               hipMemcpyDeviceToDevice, c->stream));
-      j.alpha = b.alpha;
-      j.asend = nullptr;
+      j.alpha = b.alpha;   // (asend stays null: stage_post whitens alpha)
     }
     j.G = o.G + (size_t)i * mpmax * mpmax;
     j.r = o.r + (size_t)i * mpmax;
     j.a2part = o.a2part + (size_t)i * npart;
     j.ldg = mpmax;
+    j.after = &after;
     return j;
+  }
+};
+
+// The CU-split pipeline (SplitPipe; always shared gains and np > 1: fit_pipelined).  The round's
+// head: the first output's gains on the whitening CUs, ahead of its whitening there, and the
+// others' at the same time on the Gram CUs, ahead of the first Gram; the second whitening waits
+// for them (r04j).  Tried and measured slower: every gains first, whole-chip or not;
+// the first job on the Gram CUs; the late gains beside the Grams; the first whitening whole-chip,
+// beside the others' gains (head 8.6 ms per round, r04f) or ahead of them (they then delayed the
+// second whitening and every Gram after it, r04i); the others' gains in groups on the whitening
+// stream (they delayed the Grams' DG share: 5.10 -> 5.24 ms per Gram, r04h).
+static void gram_stage_split(GramStage& s) {
+  gpar_ctx* c = s.c;
+  SplitPipe pipe(c, s.n, s.mpmax);
+  pipe.post_gram = c->post_gram == 1;
+  pipe.dg_rows_w = c->dg_rows_w == kDgRowsAuto ? 40 : c->dg_rows_w;
+  pipe.start();
+  s.gplan.launch(c->s_w, 0, 1);
+  s.gplan.launch(c->s_g2, 1, s.np - 1);
+  HIPCHECK(hipEventRecord(c->ev_gr, c->s_g2));
+  for (int i = 0; i < s.np; ++i) {
+    if (i == 1) HIPCHECK(hipStreamWaitEvent(c->s_w, c->ev_gr, 0));
+    pipe.push(s.job(i, pipe.buf[i & 1]));
+  }
+  pipe.flush();
+  if (c->mark_last) HIPCHECK(hipEventRecord(c->mark_last, c->s_g));
+  pipe.join(c->stream);   // a prediction lane's q(u) runs this on the side stream
+  // every gains launch precedes the second whitening, which join covers
+  s.copy_shared_logs();
+}
+
+// Grouped Gram: per group of gsz outputs, their whitenings and short chains alternate over the
+// context and side streams into buffers of their own, then one set of Gram launches covers the
+// whole group (grid y = output, GramGroupPtrs table), its plan sized for 1/gsz of the chip per
+// output.  A different split plan than the per-output Gram's: G moves within rounding.
+static void gram_stage_grouped(GramStage& s) {
+  gpar_ctx* c = s.c;
+  const std::vector<DevProblem>& P = s.P;
+  const int np = s.np, gsz = s.sp.gram_group;
+  const int64_t n = s.n, nch = s.nch, mpmax = s.mpmax;
+  const hipStream_t base = c->stream;
+  const int ngroups = (np + gsz - 1) / gsz;
+  auto* tab = ws<GramGroupPtrs>(c, "gram_grp_tab", (size_t)ngroups * gsz);
+  // The per-output CU share: 256 / cnt, doubled while the OFF workgroups keep >= kGrpMinRows
+  // rows each (twice the split workgroups: the eeg shard's group of 8 at N = 1e5, M = 512 went
+  // 4.46 -> 3.81 ms per Gram, OFF 10000 -> 4762 rows; dtc's 1563-row OFF slices lose 13 % when
+  // halved again: per-workgroup prologue and more partials to reduce)
+  auto plan_of = [&](int cnt) {
+    const int cus = std::max(256 / cnt, 8);
+    const GramPlan p2 = gram_plan(n, mpmax, false, 2 * cus, 2 * cus);
+    if (p2.noff > 0 && p2.rows_off >= kGrpMinRows) return p2;
+    return gram_plan(n, mpmax, false, cus, cus);
   };
-  if (split_pipe) {
-    SplitPipe sp(c, n, mpmax);
-    sp.post_gram = c->post_gram == 1;
-    sp.dg_rows_w = c->dg_rows_w == kDgRowsAuto ? 40 : c->dg_rows_w;
-    sp.start();
-    if (split_head) {
-      gplan.launch(c->s_w, 0, 1);
-      gplan.launch(c->s_g2, 1, np - 1);
-      HIPCHECK(hipEventRecord(c->ev_gr, c->s_g2));
+  // the partials, sized once for every group's plan (no buffer may move under a running launch)
+  int64_t pd = 0, rd = 0;
+  for (int cnt : {gsz, np % gsz})
+    if (cnt > 0) {
+      const GramPlan pl = plan_of(cnt);
+      pd = std::max(pd, pl.part_doubles);
+      rd = std::max(rd, pl.rpart_doubles);
     }
-    for (int i = 0; i < np; ++i) {
-      if (i == 1 && split_head) HIPCHECK(hipStreamWaitEvent(c->s_w, c->ev_gr, 0));
-      sp.push(job(i, sp.buf[i & 1]));
+  double* part = ws<double>(c, "gram_part_grp", (size_t)gsz * pd);
+  double* rpart = ws<double>(c, "gram_rpart_grp", (size_t)gsz * rd);
+  // shared gains (one grid; the outputs' transfers phi strided in one array): the group's chunk
+  // carries run as one batched launch set after its whitenings (r06: three small latency-bound
+  // launches per output were 0.8 ms of a rank's eeg round boundary, r06d trace)
+  const bool batch_post = s.sp.shared;
+  const int64_t sstr = nch * (mpmax + 1) * 4;
+  double* send_grp = batch_post ? ws<double>(c, "send_grp", (size_t)gsz * sstr) : nullptr;
+  double* cin_grp = batch_post ? ws<double>(c, "cin_grp", (size_t)gsz * sstr) : nullptr;
+  for (int g0 = 0, gi = 0; g0 < np; g0 += gsz, ++gi) {
+    const int cnt = std::min(gsz, np - g0);
+    const GramPlan plan = plan_of(cnt);
+    // the side lane starts after everything queued so far (the gains, the previous group's Gram,
+    // which still reads the buffers this group overwrites)
+    HIPCHECK(hipEventRecord(c->ev_fork, base));
+    HIPCHECK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    std::vector<StageBufs> gb(cnt);
+    std::vector<GramGroupPtrs> th_tab(cnt);
+    double work = 0.0;
+    for (int k = 0; k < cnt; ++k) {
+      const int i = g0 + k, lane = k & 1;
+      // slot k of the group, carry tags of its stream lane (reused output after output there)
+      gb[k] = stage_bufs_named(c, lane, "_g" + std::to_string(k), n, mpmax,
+                               batch_post ? send_grp + k * sstr : nullptr,
+                               batch_post ? cin_grp + k * sstr : nullptr);
+      OnStream on_(c, lane ? c->side : base);
+      const StageJob& j = s.job(i, gb[k]);
+      stage_whiten(c, j, gb[k]);
+      if (!batch_post) stage_post(c, j, gb[k], false);
+      th_tab[k] = {gb[k].beta, j.alpha, gb[k].hsum, gb[k].cin, gb[k].qv,
+                   part + (size_t)k * pd, rpart + (size_t)k * rd,
+                   j.G, j.r};
+      work += (double)P[i].n * (double)P[i].m * (double)(P[i].m + 1);
     }
-    sp.flush();
-    if (c->mark_last) HIPCHECK(hipEventRecord(c->mark_last, c->s_g));
-    sp.join(c->stream);   // a prediction lane's q(u) runs this on the side stream
-    if (split_head)       // every gains launch precedes the second whitening, which join covers
-      HIPCHECK(hipMemcpyAsync(o.logs, logs_src, (size_t)np * nch * sizeof(double),
-                              hipMemcpyDeviceToDevice, c->stream));
-    return o;
+    HIPCHECK(hipEventRecord(c->ev_join, c->side));
+    HIPCHECK(hipStreamWaitEvent(base, c->ev_join, 0));
+    if (batch_post) {   // on the context stream, after both lanes' whitenings
+      for (int k = 0; k < cnt; ++k) stage_post_head(c, s.jobs[g0 + k], gb[k]);
+      run_carry(c, P[g0].sdim, s.jobs[g0].gi.phi, s.gplan.o.phistride, send_grp, cin_grp, sstr, nch,
+                P[g0].mc, P[g0].mc, cnt, "fitc_grp");
+      check_launch("carry (grouped)");
+      for (int k = 0; k < cnt; ++k) stage_post_tail(c, s.jobs[g0 + k], gb[k], false);
+    }
+    GramGroupPtrs* dtab = tab + (size_t)gi * gsz;
+    h2d(c, dtab, th_tab.data(), (size_t)cnt);
+    wait_dense_prefix(c, &s.after);
+    {
+      Timed tm_(c, "gram", work);   // flops of every beta^T beta of the group
+      launch_gram_grouped(base, P[g0].sdim, plan, dtab, cnt, mpmax, n, P[g0].mc, kChunk, mpmax,
+                          c->side, c->ev_fork, c->ev_join);
+    }
+    check_launch("gram (grouped)");
   }
-  const int gsz = gram_group_size(c, P, n, mpmax, fix_beta, nlanes, split_pipe);
-  if (gsz >= 2) {
-    // Grouped Gram: per group of gsz outputs, their whitenings and short chains alternate over the
-    // context and side streams into buffers of their own, then one set of Gram launches covers the
-    // whole group (grid y = output, GramGroupPtrs table), its plan sized for 1/gsz of the chip per
-    // output.  A different split plan than the per-output Gram's: G moves within rounding.
-    const hipStream_t base = c->stream;
-    const int ngroups = (np + gsz - 1) / gsz;
-    auto* tab = ws<GramGroupPtrs>(c, "gram_grp_tab", (size_t)ngroups * gsz);
-    // The per-output CU share: 256 / cnt, doubled while the OFF workgroups keep >= kGrpMinRows
-    // rows each (twice the split workgroups: the eeg shard's group of 8 at N = 1e5, M = 512 went
-    // 4.46 -> 3.81 ms per Gram, OFF 10000 -> 4762 rows; dtc's 1563-row OFF slices lose 13 % when
-    // halved again: per-workgroup prologue and more partials to reduce)
-    auto plan_of = [&](int cnt) {
-      const int cus = std::max(256 / cnt, 8);
-      const GramPlan p2 = gram_plan(n, mpmax, false, 2 * cus, 2 * cus);
-      if (p2.noff > 0 && p2.rows_off >= kGrpMinRows) return p2;
-      return gram_plan(n, mpmax, false, cus, cus);
-    };
-    // the partials, sized once for every group's plan (no buffer may move under a running launch)
-    int64_t pd = 0, rd = 0;
-    for (int cnt : {gsz, np % gsz})
-      if (cnt > 0) {
-        const GramPlan pl = plan_of(cnt);
-        pd = std::max(pd, pl.part_doubles);
-        rd = std::max(rd, pl.rpart_doubles);
-      }
-    double* part = ws<double>(c, "gram_part_grp", (size_t)gsz * pd);
-    double* rpart = ws<double>(c, "gram_rpart_grp", (size_t)gsz * rd);
-    // shared gains (one grid; the outputs' transfers phi strided in one array): the group's chunk
-    // carries run as one batched launch set after its whitenings (r06: three small latency-bound
-    // launches per output were 0.8 ms of a rank's eeg round boundary, r06d trace)
-    const bool batch_post = shared;
-    const int64_t sstr = nch * (mpmax + 1) * 4;
-    double* send_grp = batch_post ? ws<double>(c, "send_grp", (size_t)gsz * sstr) : nullptr;
-    double* cin_grp = batch_post ? ws<double>(c, "cin_grp", (size_t)gsz * sstr) : nullptr;
-    for (int g0 = 0, gi = 0; g0 < np; g0 += gsz, ++gi) {
-      const int cnt = std::min(gsz, np - g0);
-      const GramPlan plan = plan_of(cnt);
-      // the side lane starts after everything queued so far (the gains, the previous group's Gram,
-      // which still reads the buffers this group overwrites)
-      HIPCHECK(hipEventRecord(c->ev_fork, base));
-      HIPCHECK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-      std::vector<StageBufs> gb(cnt);
-      std::vector<GramGroupPtrs> th_tab(cnt);
-      double work = 0.0;
-      for (int k = 0; k < cnt; ++k) {
-        const int i = g0 + k, lane = k & 1;
-        gb[k] = batch_post ? stage_bufs_grp(c, lane, k, n, mpmax, send_grp + (size_t)k * sstr,
-                                            cin_grp + (size_t)k * sstr)
-                           : stage_bufs_grp(c, lane, k, n, mpmax);
-        OnStream on_(c, lane ? c->side : base);
-        const StageJob& j = job(i, gb[k]);
-        stage_whiten(c, j, gb[k]);
-        if (!batch_post) stage_post(c, j, gb[k], false);
-        th_tab[k] = {gb[k].beta, j.alpha, gb[k].hsum, gb[k].cin, gb[k].qv,
-                     part + (size_t)k * pd, rpart + (size_t)k * rd,
-                     j.G, j.r};
-        work += (double)P[i].n * (double)P[i].m * (double)(P[i].m + 1);
-      }
-      HIPCHECK(hipEventRecord(c->ev_join, c->side));
-      HIPCHECK(hipStreamWaitEvent(base, c->ev_join, 0));
-      if (batch_post) {   // on the context stream, after both lanes' whitenings
-        for (int k = 0; k < cnt; ++k) stage_post_head(c, jobs[g0 + k], gb[k]);
-        run_carry(c, P[g0].sdim, gains[g0].phi, gplan.o.phistride, send_grp, cin_grp, sstr, nch,
-                  P[g0].mc, P[g0].mc, cnt, "fitc_grp");
-        check_launch("carry (grouped)");
-        for (int k = 0; k < cnt; ++k) stage_post_tail(c, jobs[g0 + k], gb[k], false);
-      }
-      GramGroupPtrs* dtab = tab + (size_t)gi * gsz;
-      h2d(c, dtab, th_tab.data(), (size_t)cnt);
-      if (c->gram_after) {   // the round's dense prefix (eval_dtc) first
-        HIPCHECK(hipStreamWaitEvent(base, c->gram_after, 0));
-        c->gram_after = nullptr;
-      }
-      {
-        Timed tm_(c, "gram", work);   // flops of every beta^T beta of the group
-        launch_gram_grouped(base, P[g0].sdim, plan, dtab, cnt, mpmax, n, P[g0].mc, kChunk, mpmax,
-                            c->side, c->ev_fork, c->ev_join);
-      }
-      check_launch("gram (grouped)");
+}
+
+// One lane, pipelined (the batched fit off the CU split): the big kernels stay in order on the
+// context stream, whitening(i + 1) issued ahead of Gram(i), and output i's short chain between
+// them (alpha's end states, the chunk carry, vec_fix, the beta tail) runs on the side stream
+// beside a whitening instead of on the critical path.  Two beta / carry buffers (fit_pipelined).
+// main: W0 W1 G0 W2 G1 W3 G2 ...; side: P0 after W0, P(i+1) after G(i), so P(i+1) runs beside
+// W(i+2) and G(i+1) waits for it.  (P(i+1) right after W(i+1) would start with G(i) and queue
+// G(i)'s co-running correction behind it on the side stream: 4.17 -> 4.93 ms per Gram.)
+static void gram_stage_pipelined(GramStage& s) {
+  gpar_ctx* c = s.c;
+  const int np = s.np;
+  const StageBufs bufs[2] = {stage_bufs(c, 0, s.n, s.mpmax), stage_bufs(c, 1, s.n, s.mpmax)};
+  auto issue_post = [&](int i) {
+    HIPCHECK(hipEventRecord(c->ev_pw, c->main));
+    HIPCHECK(hipStreamWaitEvent(c->side, c->ev_pw, 0));
+    {
+      OnStream on_(c, c->side);
+      stage_post(c, s.jobs[i], bufs[i & 1], false);
     }
-    return o;
+    HIPCHECK(hipEventRecord(c->ev_pc[i & 1], c->side));
+  };
+  stage_whiten(c, s.job(0, bufs[0]), bufs[0]);
+  issue_post(0);
+  for (int i = 0; i < np; ++i) {
+    if (i + 1 < np) stage_whiten(c, s.job(i + 1, bufs[(i + 1) & 1]), bufs[(i + 1) & 1]);
+    HIPCHECK(hipStreamWaitEvent(c->main, c->ev_pc[i & 1], 0));
+    stage_gram(c, s.jobs[i], bufs[i & 1], false, false, "", c->side, 256);
+    if (i + 1 < np) issue_post(i + 1);
   }
+  // every side-stream item has been waited for: P(np-1) by G(np-1), the corrections by their Gram
+}
+
+// Output by output, over one lane or two.  Two (gpar_ctx_set_lanes): the outputs alternate between
+// the context stream and the side stream, each with its own beta / alpha / carry workspace, so one
+// output's (VALU-bound) whitening overlaps another's (MFMA-bound) Gram; gains are shared, so the
+// side stream waits for them (fork event).  One: the caller's stream (a prediction lane's q(u) may
+// run on the side stream; its Gram's co-running correction then goes to main).
+static void gram_stage_lanes(GramStage& s) {
+  gpar_ctx* c = s.c;
+  const int nlanes = s.sp.nlanes;
   StageBufs bufs[2];
-  const int nbuf = (nlanes > 1 || pipe) ? 2 : 1;
-  for (int l = 0; l < nbuf; ++l) bufs[l] = stage_bufs(c, l, n, mpmax);
+  for (int l = 0; l < nlanes; ++l) bufs[l] = stage_bufs(c, l, s.n, s.mpmax);
   if (nlanes > 1) {
     HIPCHECK(hipEventRecord(c->ev_fork, c->stream));
     HIPCHECK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
   }
-  if (pipe) {
-    // main: W0 W1 G0 W2 G1 W3 G2 ...; side: P0 after W0, P(i+1) after G(i), so P(i+1) runs beside
-    // W(i+2) and G(i+1) waits for it.  (P(i+1) right after W(i+1) would start with G(i) and queue
-    // G(i)'s co-running correction behind it on the side stream: 4.17 -> 4.93 ms per Gram.)
-    auto issue_post = [&](int i) {
-      HIPCHECK(hipEventRecord(c->ev_pw, c->main));
-      HIPCHECK(hipStreamWaitEvent(c->side, c->ev_pw, 0));
-      {
-        OnStream on_(c, c->side);
-        stage_post(c, jobs[i], bufs[i % nbuf], false);
-      }
-      HIPCHECK(hipEventRecord(c->ev_pc[i & 1], c->side));
-    };
-    stage_whiten(c, job(0, bufs[0]), bufs[0]);
-    issue_post(0);
-    for (int i = 0; i < np; ++i) {
-      if (i + 1 < np) stage_whiten(c, job(i + 1, bufs[(i + 1) % nbuf]), bufs[(i + 1) % nbuf]);
-      HIPCHECK(hipStreamWaitEvent(c->main, c->ev_pc[i & 1], 0));
-      stage_gram(c, jobs[i], bufs[i % nbuf], false, false, "", c->side, 256);
-      if (i + 1 < np) issue_post(i + 1);
-    }
-    // every side-stream item has been waited for: P(np-1) by G(np-1), the corrections by their Gram
-    return o;
-  }
-  // one lane: the caller's stream (a prediction lane's q(u) may run on the side stream; its
-  // Gram's co-running correction then goes to main)
   const hipStream_t base = c->stream;
   const hipStream_t helper = base == c->side ? c->main : c->side;
-  for (int i = 0; i < np; ++i) {
+  for (int i = 0; i < s.np; ++i) {
     const int lane = i % nlanes;
-    const StageBufs& b = bufs[i % nbuf];
+    const StageBufs& b = bufs[lane];
     OnStream on_(c, lane ? c->side : base);
-    const StageJob& j = job(i, b);
+    const StageJob& j = s.job(i, b);
     stage_whiten(c, j, b);
-    stage_post(c, j, b, fix_beta);
-    stage_gram(c, j, b, fix_beta, nlanes > 1, (nlanes > 1 && lane) ? "_1" : "",
-               nlanes == 1 ? helper : nullptr, 256);
+    stage_post(c, j, b, s.fix_beta);
+    stage_gram(c, j, b, s.fix_beta, nlanes > 1, lane ? "_1" : "", nlanes == 1 ? helper : nullptr,
+               256);
   }
   if (nlanes > 1) {   // join: the dense tail on the context stream needs every G
     HIPCHECK(hipEventRecord(c->ev_join, c->side));
     HIPCHECK(hipStreamWaitEvent(c->main, c->ev_join, 0));
   }
-  return o;
+}
+
+GramOut run_gram_stage(gpar_ctx* c, const std::vector<DevProblem>& P,
+                       const std::vector<Theta>& th, bool fix_beta, hipEvent_t after) {
+  GramStage s(c, P, th, fix_beta, after);
+  if (s.sp.split) gram_stage_split(s);
+  else if (s.sp.gram_group >= 2) gram_stage_grouped(s);
+  else if (s.sp.pipelined) gram_stage_pipelined(s);
+  else gram_stage_lanes(s);
+  return s.o;
 }
 
 // L_u = chol(Kuu [+ s2 I]), T_u = L_u^-1, Lambda = T_u G T_u^T + I, L_lam = chol(Lambda) for
@@ -603,9 +613,8 @@ void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<T
   // chain ("head_p0") -> the first Gram's start ("head_gram_wait") -> the last Gram's end
   // ("round_grams") -> the values on the host ("round_tail")
   gpar_ctx::MarkSeq seq;
-  int64_t mpm = 0;
-  for (const auto& p : P) mpm = std::max(mpm, p.mp);
-  if (c->profiling && fit_pipelined(c, P) && split_active(c, P[0].n, mpm)) {   // SplitPipe marks
+  const StagePlan sp = stage_plan(c, P);   // the schedule run_gram_stage will take
+  if (c->profiling && sp.split) {   // SplitPipe marks
     seq.names = {"", "head_gains", "head_w0", "head_p0", "head_gram_wait", "round_grams",
                  "round_tail"};
     seq.ev.assign(seq.names.size(), nullptr);
@@ -632,39 +641,29 @@ void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<T
   // while the Gram CUs would otherwise wait, instead of after the round's last Gram.  (On the
   // dense stream over the whitening CUs instead, r04e, it slowed every Gram 5.11 -> 5.16 ms: the
   // Gram's diagonal-block share runs there.)
-  int64_t mpmax = 0;
-  for (const auto& p : P) mpmax = std::max(mpmax, p.mp);
-  const bool early = c->dense_early && fit_pipelined(c, P) && split_active(c, P[0].n, mpmax);
+  const bool early = c->dense_early && sp.split;
   // Unsplit batched rounds (the dtc / eeg configs, a rank's eeg shard): the same G-independent
   // half on the dense stream (s_d), beside the round's gains, whitenings and Grams instead of
   // after the last Gram -- a chain of latency-bound 64 x 64 launches (eeg shard 0/8, r06d trace:
   // 2.2 ms of a 5.3 ms round boundary was the dense tail)
   const bool early_side = !early && c->dense_early && P.size() > 1 && c->s_d != nullptr;
   DenseOut dn{};
-  if (early_side) {
+  if (early || early_side) {
+    // early: the Gram stream first follows everything queued on the context stream (host inputs'
+    // uploads, the pseudo-input centres, the distance cache), then factors Kuu beside the round's
+    // gains (on a Gram-CU stream of its own, r04ae, the first Gram no longer queued behind it but
+    // shared the Gram CUs with it: 17.67 -> 17.70 s per job).  early_side: the same on s_d; the
+    // round's first Gram waits for it (run_gram_stage's `after`)
+    const hipStream_t st = early ? c->s_g : c->s_d;
     HIPCHECK(hipEventRecord(c->ev_dn, c->stream));
-    HIPCHECK(hipStreamWaitEvent(c->s_d, c->ev_dn, 0));
-    OnStream on_(c, c->s_d);
-    dn = run_dense_pre(c, P, th, mpmax, false);
-    HIPCHECK(hipEventRecord(c->ev_dn, c->s_d));
-    c->gram_after = c->ev_dn;
+    HIPCHECK(hipStreamWaitEvent(st, c->ev_dn, 0));
+    OnStream on_(c, st);
+    dn = run_dense_pre(c, P, th, sp.mpmax, false);
+    if (early_side) HIPCHECK(hipEventRecord(c->ev_dn, st));
   }
-  if (early) {
-    // the Gram stream first follows everything queued on the context stream (host inputs' uploads,
-    // the pseudo-input centres, the distance cache), then factors Kuu beside the round's gains
-    // (on a Gram-CU stream of its own, r04ae, the first Gram no longer queued behind it but shared
-    // the Gram CUs with it: 17.67 -> 17.70 s per job)
-    HIPCHECK(hipEventRecord(c->ev_dn, c->stream));
-    HIPCHECK(hipStreamWaitEvent(c->s_g, c->ev_dn, 0));
-    OnStream on_(c, c->s_g);
-    dn = run_dense_pre(c, P, th, mpmax, false);
-  }
-  GramOut go = run_gram_stage(c, P, th);
+  GramOut go = run_gram_stage(c, P, th, false, early_side ? c->ev_dn : nullptr);
   if (gram_out) *gram_out = go;
-  if (early_side) {
-    c->gram_after = nullptr;   // (consumed by the first Gram; cleared if there was none)
-    HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_dn, 0));
-  }
+  if (early_side) HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_dn, 0));
   else if (!early) dn = run_dense_pre(c, P, th, go.ldg, false);
   run_dense_post(c, P, go, dn);
   const int64_t nch = P[0].nch;

@@ -70,8 +70,9 @@ std::vector<QuPre> run_q_u_batch(gpar_ctx* c, const std::vector<DevProblem>& P,
                                         const std::vector<Theta>& T, const FitKeep& keep,
                                         bool want_cov) {
   const int np = (int)P.size();
-  int64_t mpmax = 0, mmax = 0;
-  for (const auto& p : P) { mpmax = std::max(mpmax, p.mp); mmax = std::max(mmax, p.m); }
+  const int64_t mpmax = max_mp(P);
+  int64_t mmax = 0;
+  for (const auto& p : P) mmax = std::max(mmax, p.m);
   const bool qn = P[0].qu_noise;
   bool kept = qn;   // the fit's Grams serve the regularised convention only (run_q_u)
   for (int i = 0; i < np; ++i)
@@ -330,7 +331,7 @@ void predict_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem,
     if (st) throw Error(GPAR_ERR_NOT_PD, "PosDefException: cholesky(Symmetric(inv(D))) failed (MvNormal, gpar_scaled_inference.jl:185)");
   };
   // ---- gains on the merged grid (noise sigma^2 train / 1e10 test)
-  std::vector<ChainParamsHost> cps{{1.0 / th.l_t, th.l_t, th.sv_t * th.sv_t, s2}};
+  std::vector<ChainParamsHost> cps{chain_params_of(th, s2)};
   const bool path = mode == GPAR_PREDICT_PATH;
   GainsOut g;
   if (prep) {   // computed ahead on the side stream (gpar_posterior_prepare)
@@ -971,7 +972,7 @@ int32_t gpar_posterior_prepare(gpar_ctx* ctx, const gpar_posterior* post, int32_
     launch_merge_side(ctx->stream, t_star, n_star, P.t, P.n, 1, nullptr, 1e10, nullptr, 0, 0, tm, ym,
                       rm, nullptr, 0, nullptr);
     check_launch("prepare: merge");
-    std::vector<ChainParamsHost> cps{{1.0 / o.th.l_t, o.th.l_t, o.th.sv_t * o.th.sv_t, s2}};
+    std::vector<ChainParamsHost> cps{chain_params_of(o.th, s2)};
     s.g = run_gains(ctx, P.sdim, tm, nt, cps, rm, false, tag);
     s.h = ws<double>(ctx, tag + "_h", (size_t)nt * 4);
     launch_gains_adjoint(ctx->stream, P.sdim, s.g.rec, nt, kChunk, nch, 1, s.h);

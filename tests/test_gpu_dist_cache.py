@@ -75,7 +75,7 @@ def _split_batch(kernel, n=70_000, m=64, dims=(1, 4, 16)):
 
 @pytest.mark.parametrize("kernel", ["matern52", "eq", "matern12"])
 def test_split_fit_caches_every_output(kernel):
-    """With the CU split on and N >= 2^16 the fit caches outputs down to D = 1 (gpar_host.cpp
+    """With the CU split on and N >= 2^16 the fit caches outputs down to D = 1 (host_fit.cpp
     attach_dist_cache): the small-D cached path (group-centred Gram-form distances, or direct
     differences for Matern-1/2) against the same split fit without the cache, and one output's
     objective at the fitted theta against the C port (dtc.jl:83-128)."""

@@ -1,7 +1,7 @@
 """Parity of the bench's headline schedule.
 
 bench.py's north job runs the batched fit on the schedule that only engages on big problems: the
-auto CU split (N Mp^2 >= 1e11, gpar_host.cpp split_active), the pipelined Gram stage and the
+auto CU split (N Mp^2 >= 1e11, host.hpp split_active), the pipelined Gram stage and the
 distance cache down to D = 1 (N >= 2^16 on the split), q(u) reusing the fit's Gram at the fitted
 theta.  Here that schedule runs un-forced at N = 4e5, M = 512 (N Mp^2 = 1.05e11) over five outputs
 with D = 1, 2, 8, 16, 32, HBM-resident inputs laid out as the bench lays them (V a column slice of
