@@ -27,6 +27,7 @@
 
 namespace gpar {
 struct PredPrep;
+struct ScaledGram;
 constexpr int kDgRowsAuto = -100;   // gpar_ctx::dg_rows_w "auto"
 }
 
@@ -108,6 +109,12 @@ struct gpar_ctx {
   // other group's tails and gains (the 8-output shard 3/8, r05r: 2.278 s at 0, 2.244 at +20,
   // 2.304 at +40; with the r04 whitening 0 was best, r04ad)
   int dg_rows_w = gpar::kDgRowsAuto;
+  // "scaled_gram": a batched fit keeps every output's first Gram of the call and serves the
+  // evaluations that differ from it only in sv_o by rescaling it (ScaledGram): 1, 0 = every
+  // evaluation runs its whitening and Gram.  A plan like dg_rows_w: bit-identical to its
+  // serialized twin, within rounding of 0.
+  int scaled_gram = 1;
+  gpar::ScaledGram* sgram = nullptr;   // the running fit call's slots (fit_impl), else null
   // "serialize": side, s_w, s_g, s_g2 and s_d all alias `main`, so every launch runs in issue order
   // on one stream (the created streams stay in own_*): the order-free reference the concurrent
   // schedule must equal bit for bit.  Plans, CU shares of work items and workspaces are unchanged.
@@ -284,6 +291,7 @@ struct DevProblem {
   const double* d2 = nullptr;
   bool d2_is_r = false;
   int cache_slot = -1;   // its gpar_ctx::cache_valid entry (an OOM eviction clears it)
+  int fit_idx = -1;      // its output index in the running fit call (ScaledGram slot), else -1
 };
 
 // The cached distances of p if they are still resident, else null (fused kernel).
@@ -519,6 +527,35 @@ struct SplitPipe {
 GramOut run_gram_stage(gpar_ctx* c, const std::vector<DevProblem>& P,
                        const std::vector<Theta>& th, bool fix_beta = false,
                        hipEvent_t after = nullptr);
+
+// Kfu = s_o kappa(r / l_o) with s_o = sv_o^2 and the filter does not see s_o, so an evaluation
+// that differs from another of the same output only in sv_o has G and r scaled by c^2 and c,
+// c = (sv_o' / sv_o)^2, and the same alpha^2 and log S sums.  Every fit's initial simplex moves one
+// coordinate per vertex (nelder_mead.hpp), so its sv_o vertex is such an evaluation of its first.
+// A batched fit call keeps one reference slot per output: theta of the output's first evaluation of
+// the call and that evaluation's Gram-stage results (written when its Gram stage is queued; whether
+// its dense tail then fails does not matter).  A round whose every output matches its slot (equal
+// bit for bit in l_t, sv_t, l_o, sigma; sv_o different) runs no gains, whitening, chain or Gram:
+// one launch fills the round's GramOut from the slots (scaled_gram_fill).  Rounds in which only
+// some outputs match run as before -- budget-ended fits step in lock-step, so theirs all match.
+struct ScaledGram {
+  struct Slot {
+    bool have = false;
+    Theta th{};
+  };
+  std::vector<Slot> slot;          // by DevProblem::fit_idx
+  double *G = nullptr, *r = nullptr, *a2part = nullptr, *logs = nullptr;   // per slot
+  int64_t ld = 0, npart = 0, nch = 0;   // slot i: G + i ld^2 (ld = the call's widest mp), ...
+};
+// every problem of the round has a slot that th matches but for sv_o
+bool scaled_gram_applies(const gpar_ctx* c, const std::vector<DevProblem>& P,
+                         const std::vector<Theta>& th);
+// go's slots of the round from the reference slots, on c->stream (padding of narrower outputs zeroed)
+void scaled_gram_fill(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<Theta>& th,
+                      const GramOut& go);
+// the round's results into the slots of the outputs that have none yet, on c->stream
+void scaled_gram_keep(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<Theta>& th,
+                      const GramOut& go);
 
 // --------------------------------------------------------------------------- dense tail
 struct DenseOut {

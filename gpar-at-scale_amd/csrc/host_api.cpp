@@ -104,6 +104,7 @@ static constexpr Knob kKnobs[] = {
     {"post_gram", &gpar_ctx::post_gram, -1, 1, 0},
     {"compact_rec", &gpar_ctx::compact_rec, -1, 1, 0},
     {"dg_rows_w", &gpar_ctx::dg_rows_w, -50, 100, kDgRowsAuto},
+    {"scaled_gram", &gpar_ctx::scaled_gram, 0, 1, 0, true},
     {"gram_group", &gpar_ctx::gram_group, -1, 64, 0},
     {"fit_chunks", &gpar_ctx::fit_chunks, -1, 4096, 0},
     {"device_nm", &gpar_ctx::device_nm, 0, 1, 0},

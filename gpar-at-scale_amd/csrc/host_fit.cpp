@@ -309,10 +309,10 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
   // a group's dense tail + finish on the context stream as soon as its round's last Gram is
   // issued; its values land in pinned memory, ev_grp[g] marks them
   // (on the whitening CUs: beside the Gram on the whole chip it slowed every Gram by ~5 %)
-  auto issue_dense = [&](OverlapGroup& G, int64_t job) {
+  auto issue_dense = [&](OverlapGroup& G, hipEvent_t grams_done) {
     OnStream on_(c, c->s_d);
     StagingScope st_(c, G.id);
-    HIPCHECK(hipStreamWaitEvent(c->s_d, c->ev_gd[job & 1], 0));
+    HIPCHECK(hipStreamWaitEvent(c->s_d, grams_done, 0));
     const int na = (int)G.act.size();
     DenseOut dn = run_dense(c, G.sub, G.th, G.go, false);
     std::vector<Finish2JobHost> fj(na);
@@ -326,12 +326,33 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
     HIPCHECK(hipEventRecord(c->ev_grp[G.id], c->s_d));
   };
   sp.on_gram = [&](const StageJob& j, int64_t job) {
-    if (j.last) issue_dense(grp[j.group], job);
+    if (!j.last) return;
+    OverlapGroup& G = grp[j.group];
+    {   // the group's first evaluations into their reference slots (ScaledGram), behind its Grams
+      OnStream on_(c, c->s_g);
+      StagingScope st_(c, G.id);
+      scaled_gram_keep(c, G.sub, G.th, G.go);
+    }
+    issue_dense(G, c->ev_gd[job & 1]);
   };
   // ask every active member for its next point; queue the group's gains and its jobs
   auto begin_round = [&](OverlapGroup& G) {
     if (!ask_group(c, G, nm, P)) return;
     const int na = (int)G.act.size();
+    if (scaled_gram_applies(c, G.sub, G.th)) {
+      // every member's Gram is a rescaling of its kept one: one launch on the Gram stream (behind
+      // the kept points' copies and the slots' writes) instead of the round's gains and jobs,
+      // then the group's tail as after a last Gram (ev_gn: no gains this round)
+      {
+        OnStream on_(c, c->s_g);
+        StagingScope st_(c, G.id);
+        scaled_gram_fill(c, G.sub, G.th, G.go);
+        HIPCHECK(hipEventRecord(c->ev_gn[G.id], c->s_g));
+      }
+      issue_dense(G, c->ev_gn[G.id]);
+      G.in_flight = true;
+      return;
+    }
     std::vector<ChainParamsHost> cps(na);
     std::vector<const double*> ys(na);
     for (int a = 0; a < na; ++a) {
@@ -638,9 +659,29 @@ void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* lo
                            later_bytes);
   }
   CacheRelease release_{ctx};   // the cache lives for this fit call only
-  const std::vector<DevProblem> P =
-      attach_dist_cache(ctx, P0, fit_ws_estimate(ctx, P0) + later_bytes);
+  std::vector<DevProblem> P = attach_dist_cache(ctx, P0, fit_ws_estimate(ctx, P0) + later_bytes);
   const int nprob = (int)P.size();
+  // the reference slots of the rescaled Gram (ScaledGram), for this call only (8 Mp^2 bytes per
+  // output, out of the cache budget's reserve: counted in fit_ws_estimate, their 132 MB at north
+  // cost the auto budget a 4 GB cache slot)
+  ScaledGram sgram;
+  struct SgramScope {
+    gpar_ctx* c;
+    ~SgramScope() { c->sgram = nullptr; }
+  } sgram_scope_{ctx};
+  if (ctx->scaled_gram) {
+    for (int i = 0; i < nprob; ++i) P[i].fit_idx = i;
+    sgram.slot.assign(nprob, {});
+    sgram.ld = max_mp(P);
+    sgram.nch = P[0].nch;
+    sgram.npart = vec_fix_blocks(P[0].n);
+    sgram.G = ws<double>(ctx, "sgram_G", (size_t)nprob * sgram.ld * sgram.ld);
+    sgram.r = ws<double>(ctx, "sgram_r", (size_t)nprob * sgram.ld);
+    sgram.a2part = ws<double>(ctx, "sgram_a2", (size_t)nprob * sgram.npart);
+    sgram.logs = ws<double>(ctx, "sgram_logs", (size_t)nprob * sgram.nch);
+    (void)ws<GramScaleJob>(ctx, "sgram_jobs", (size_t)nprob);
+    ctx->sgram = &sgram;
+  }
   // the whole fit after its distance cache, on the context stream (every schedule ends joined to it
   // or synchronised): the bench's fit time against its Gram spans
   std::optional<Timed> tm_fit;

@@ -507,6 +507,90 @@ GramOut run_gram_stage(gpar_ctx* c, const std::vector<DevProblem>& P,
   return s.o;
 }
 
+// ---------------------------------------------------------------- rescaled Gram (ScaledGram)
+bool scaled_gram_applies(const gpar_ctx* c, const std::vector<DevProblem>& P,
+                         const std::vector<Theta>& th) {
+  const ScaledGram* sg = c->sgram;
+  if (!sg || P.empty()) return false;
+  for (size_t i = 0; i < P.size(); ++i) {
+    const int f = P[i].fit_idx;
+    if (f < 0 || f >= (int)sg->slot.size() || !sg->slot[f].have) return false;
+    const Theta& a = sg->slot[f].th;
+    const Theta& b = th[i];
+    if (!(a.l_t == b.l_t && a.sv_t == b.sv_t && a.l_o == b.l_o && a.sigma == b.sigma &&
+          a.sv_o != b.sv_o))
+      return false;
+  }
+  return true;
+}
+
+// jobs between the round's GramOut slots and the reference slots, uploaded and launched on c->stream
+static void scaled_gram_launch(gpar_ctx* c, std::vector<GramScaleJob>& jobs, int64_t mpmax) {
+  if (jobs.empty()) return;
+  auto* dj = ws<GramScaleJob>(c, "sgram_jobs", c->sgram->slot.size());
+  h2d(c, dj, jobs.data(), jobs.size());
+  launch_gram_scale(c->stream, dj, (int)jobs.size(), mpmax);
+  check_launch("gram_scale");
+}
+
+void scaled_gram_fill(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<Theta>& th,
+                      const GramOut& go) {
+  const ScaledGram& sg = *c->sgram;
+  const int64_t ld = go.ldg;
+  std::vector<GramScaleJob> jobs;
+  for (size_t i = 0; i < P.size(); ++i) {
+    const DevProblem& p = P[i];
+    const size_t f = (size_t)p.fit_idx;
+    if (p.mp != ld) {   // the dense tail reads the slot's padding as zero
+      HIPCHECK(hipMemsetAsync(go.G + i * ld * ld, 0, (size_t)ld * ld * sizeof(double), c->stream));
+      HIPCHECK(hipMemsetAsync(go.r + i * ld, 0, (size_t)ld * sizeof(double), c->stream));
+    }
+    const double q = th[i].sv_o / sg.slot[f].th.sv_o;
+    jobs.push_back({sg.G + f * sg.ld * sg.ld, sg.r + f * sg.ld, sg.a2part + f * sg.npart,
+                    sg.logs + f * sg.nch, go.G + i * ld * ld, go.r + i * ld,
+                    go.a2part + i * go.npart, go.logs + i * sg.nch, sg.ld, ld, p.mp, sg.npart,
+                    sg.nch, q * q});
+  }
+  scaled_gram_launch(c, jobs, ld);
+}
+
+void scaled_gram_keep(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<Theta>& th,
+                      const GramOut& go) {
+  ScaledGram* sg = c->sgram;
+  if (!sg) return;
+  const int64_t ld = go.ldg;
+  std::vector<GramScaleJob> jobs;
+  for (size_t i = 0; i < P.size(); ++i) {
+    const DevProblem& p = P[i];
+    const int f = p.fit_idx;
+    if (f < 0 || f >= (int)sg->slot.size() || sg->slot[f].have) continue;
+    jobs.push_back({go.G + i * ld * ld, go.r + i * ld, go.a2part + i * go.npart,
+                    go.logs + i * sg->nch, sg->G + (size_t)f * sg->ld * sg->ld,
+                    sg->r + (size_t)f * sg->ld, sg->a2part + (size_t)f * sg->npart,
+                    sg->logs + (size_t)f * sg->nch, ld, sg->ld, p.mp, sg->npart, sg->nch, 1.0});
+    sg->slot[f].have = true;
+    sg->slot[f].th = th[i];
+  }
+  scaled_gram_launch(c, jobs, ld);
+}
+
+// The Gram-stage results of a round whose every output matches its reference slot, in the
+// workspace slots run_gram_stage would have filled.
+static GramOut scaled_gram_stage(gpar_ctx* c, const std::vector<DevProblem>& P,
+                                 const std::vector<Theta>& th) {
+  const int np = (int)P.size();
+  const int64_t n = P[0].n, nch = (n + kChunk - 1) / kChunk, mpmax = max_mp(P);
+  GramOut o{};
+  o.ldg = mpmax;
+  o.npart = vec_fix_blocks(n);
+  o.G = ws<double>(c, "G", (size_t)np * mpmax * mpmax);
+  o.r = ws<double>(c, "r", (size_t)np * mpmax);
+  o.a2part = ws<double>(c, "a2part", (size_t)np * o.npart);
+  o.logs = ws<double>(c, "logs_all", (size_t)np * nch);
+  scaled_gram_fill(c, P, th, o);
+  return o;
+}
+
 // L_u = chol(Kuu [+ s2 I]), T_u = L_u^-1, Lambda = T_u G T_u^T + I, L_lam = chol(Lambda) for
 // every problem: blocked 64 x 64 MFMA kernels (k_chol.hip), matrices padded with identity to
 // ld = Mp (padding contributes log 1 = 0 and zero right-hand sides).  run_dense_pre is the part
@@ -614,7 +698,10 @@ void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<T
   // ("round_grams") -> the values on the host ("round_tail")
   gpar_ctx::MarkSeq seq;
   const StagePlan sp = stage_plan(c, P);   // the schedule run_gram_stage will take
-  if (c->profiling && sp.split) {   // SplitPipe marks
+  // every output's Gram a rescaling of its kept one (ScaledGram): no Gram stage this round, the
+  // dense tail whole on the context stream behind the rescaling launch
+  const bool rescaled = scaled_gram_applies(c, P, th);
+  if (c->profiling && sp.split && !rescaled) {   // SplitPipe marks
     seq.names = {"", "head_gains", "head_w0", "head_p0", "head_gram_wait", "round_grams",
                  "round_tail"};
     seq.ev.assign(seq.names.size(), nullptr);
@@ -641,12 +728,13 @@ void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<T
   // while the Gram CUs would otherwise wait, instead of after the round's last Gram.  (On the
   // dense stream over the whitening CUs instead, r04e, it slowed every Gram 5.11 -> 5.16 ms: the
   // Gram's diagonal-block share runs there.)
-  const bool early = c->dense_early && sp.split;
+  const bool early = c->dense_early && sp.split && !rescaled;
   // Unsplit batched rounds (the dtc / eeg configs, a rank's eeg shard): the same G-independent
   // half on the dense stream (s_d), beside the round's gains, whitenings and Grams instead of
   // after the last Gram -- a chain of latency-bound 64 x 64 launches (eeg shard 0/8, r06d trace:
   // 2.2 ms of a 5.3 ms round boundary was the dense tail)
-  const bool early_side = !early && c->dense_early && P.size() > 1 && c->s_d != nullptr;
+  const bool early_side =
+      !early && !rescaled && c->dense_early && P.size() > 1 && c->s_d != nullptr;
   DenseOut dn{};
   if (early || early_side) {
     // early: the Gram stream first follows everything queued on the context stream (host inputs'
@@ -661,7 +749,9 @@ void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<T
     dn = run_dense_pre(c, P, th, sp.mpmax, false);
     if (early_side) HIPCHECK(hipEventRecord(c->ev_dn, st));
   }
-  GramOut go = run_gram_stage(c, P, th, false, early_side ? c->ev_dn : nullptr);
+  GramOut go = rescaled ? scaled_gram_stage(c, P, th)
+                        : run_gram_stage(c, P, th, false, early_side ? c->ev_dn : nullptr);
+  if (!rescaled) scaled_gram_keep(c, P, th, go);
   if (gram_out) *gram_out = go;
   if (early_side) HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_dn, 0));
   else if (!early) dn = run_dense_pre(c, P, th, go.ldg, false);

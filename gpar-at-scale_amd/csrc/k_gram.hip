@@ -642,6 +642,23 @@ __global__ __launch_bounds__(256) void gram2_reduce(const double* __restrict__ p
   G[gc * ldg + gr] = s;
 }
 
+// The Gram-stage results of an evaluation that differs from a kept one only in the output
+// kernel's variance s_o = sv_o^2 (GramScaleJob): Kfu, beta and the correction's H_j, C_j are linear
+// in s_o and the filter does not see it, so G and r scale by c^2 and c = s_o' / s_o, and the
+// alpha^2 / log S partials are the kept ones.  Grid (rows, jobs): block x takes row x of G; block 0
+// also r and the partials.
+__global__ __launch_bounds__(256) void gram_scale_kernel(const GramScaleJob* __restrict__ jobs) {
+  const GramScaleJob j = jobs[blockIdx.y];
+  const int64_t row = blockIdx.x;
+  if (row >= j.mp) return;
+  const double c2 = j.c * j.c;
+  for (int64_t q = threadIdx.x; q < j.mp; q += 256) j.Gd[row * j.ldd + q] = c2 * j.G[row * j.lds + q];
+  if (row != 0) return;
+  for (int64_t q = threadIdx.x; q < j.mp; q += 256) j.rd[q] = j.c * j.r[q];
+  for (int64_t q = threadIdx.x; q < j.npart; q += 256) j.a2d[q] = j.a2part[q];
+  for (int64_t q = threadIdx.x; q < j.nch; q += 256) j.logsd[q] = j.logs[q];
+}
+
 // Materialise the corrected beta (only for the (dtc, A) parity entry point).
 template <int D>
 __global__ __launch_bounds__(256) void beta_fix_kernel(double* __restrict__ beta, int64_t ldb,
@@ -871,6 +888,11 @@ void launch_gram_grouped(hipStream_t st, int sdim, const GramPlan& plan, const G
   gram3_reduce<<<dim3((unsigned)nrows, (unsigned)ngrp), 256, 0, st>>>(
       nullptr, nullptr, plan.npan, plan.noff, plan.ndg, plan.soff, plan.sdg, ncs, nullptr, ldg,
       nullptr, grp);
+}
+
+void launch_gram_scale(hipStream_t st, const GramScaleJob* jobs_dev, int njobs, int64_t mpmax) {
+  if (njobs <= 0 || mpmax <= 0) return;
+  gram_scale_kernel<<<dim3((unsigned)mpmax, (unsigned)njobs), 256, 0, st>>>(jobs_dev);
 }
 
 void launch_beta_fix(hipStream_t st, int sdim, double* beta, int64_t ldb, int64_t n,

@@ -96,6 +96,16 @@ struct GramGroupPtrs {
   double* r;
 };
 
+// One output's Gram-stage results taken from another evaluation's (launch_gram_scale):
+// Gd = c^2 G (mp x mp), rd = c r (mp), the alpha^2 and log S partials copied.  c = 1 copies.
+struct GramScaleJob {
+  const double *G, *r, *a2part, *logs;
+  double *Gd, *rd, *a2d, *logsd;
+  int64_t lds, ldd;   // leading dimensions of G and Gd
+  int64_t mp, npart, nch;
+  double c;
+};
+
 constexpr int kGramTile = 128;
 constexpr int kBKRows = 16;   // the Gram kernels' time rows per K-step (gram_common.hpp kBK)
 constexpr int kRecStride3 = 16;
@@ -227,6 +237,8 @@ void launch_gram_grouped(hipStream_t st, int sdim, const GramPlan& plan, const G
                          hipStream_t side, hipEvent_t ev_a, hipEvent_t ev_b);
 void launch_beta_fix(hipStream_t st, int sdim, double* beta, int64_t ldb, int64_t n,
                      const double* g, const double* cin, int64_t mc, int L);
+// mpmax: the widest job's mp (grid x = rows)
+void launch_gram_scale(hipStream_t st, const GramScaleJob* jobs_dev, int njobs, int64_t mpmax);
 
 // k_dense.hip
 void launch_kuu(hipStream_t st, const KuuJobHost* jobs_dev, int njobs, int mmax);

@@ -175,6 +175,15 @@ int32_t gpar_ctx_set_predict_fused(gpar_ctx* ctx, int32_t on);
  *                   split Gram, fewer on the Gram CUs; -100 (default) = auto: 40 in the
  *                   round-by-round fit, 20 in the round overlap (changes G's summation grouping:
  *                   last bits, like predict_fused)
+ *   "scaled_gram"   1 (default): a batched fit keeps each output's first Gram of the call (G, r and
+ *                   the alpha^2 / log S sums, 8 Mp^2 bytes per output) and serves the evaluations
+ *                   whose theta equals that one's bit for bit in (l_t, sv_t, l_o, sigma) and
+ *                   differs in sv_o -- every fit's fifth, the sv_o vertex of the initial simplex --
+ *                   as G' = c^2 G, r' = c r, c = (sv_o' / sv_o)^2, in rounds where every output
+ *                   of the round matches; such a round runs no gains, whitening or Gram.  0: every
+ *                   evaluation computes its own.  A plan like dg_rows_w: bit-identical to its
+ *                   serialized twin, last bits against 0.  gpar_dtc_objective*, q(u) and the
+ *                   predictions never rescale (the Gram gpar_fit_predict keeps for q(u) may be one)
  *   "gram_group"    outputs per grouped Gram of an unsplit batched fit: the group's outputs whiten
  *                   over two streams into buffers of their own and one set of Gram launches covers
  *                   them all (grid y = output), each with 1/g of the time splits; -1 (default) =
