@@ -114,6 +114,12 @@ struct gpar_ctx {
   // evaluation runs its whitening and Gram.  A plan like dg_rows_w: bit-identical to its
   // serialized twin, within rounding of 0.
   int scaled_gram = 1;
+  // "chain_mean_first": gpar_fit_predict_chain (device memory, ANALYTIC) runs only each output's
+  // mean-only prediction (predict_mean_impl) in chain order on the context stream; the full
+  // predictions, which supply the stds, follow on the side stream's lane.  0 (default): the full
+  // prediction per output in chain order.  The means are the mean-only path's (within rounding
+  // of 0's); bit-identical to its serialized twin.
+  int chain_mean_first = 0;
   gpar::ScaledGram* sgram = nullptr;   // the running fit call's slots (fit_impl), else null
   // "serialize": side, s_w, s_g, s_g2 and s_d all alias `main`, so every launch runs in issue order
   // on one stream (the created streams stay in own_*): the order-free reference the concurrent
@@ -655,6 +661,18 @@ void predict_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem,
                          int64_t ldvs, int mode, int samples, uint64_t seed, double* mean_out,
                          double* std_out, const GramCache* gc = nullptr, bool defer = false,
                          const QuPre* pre = nullptr, const PredPrep* prep = nullptr);
+// The ANALYTIC mean of predict_impl without its variance: f = Cf*u w by launch_kfu_gemv and a
+// one-column smoother of y* - f on the merged grid, O((n + n*) m d) work and O(n + n*) workspace.
+// xtr (optional): the training rows' y - Kfu w (kfu_train_residual), which depends only on the
+// posterior; null: computed here.  pre / prep / defer as predict_impl's.
+void kfu_train_residual(gpar_ctx* c, const DevProblem& P, const Theta& th, const double* w,
+                        double* xtr);
+void predict_mean_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem, int64_t n_star,
+                       const double* t_star_in, const double* v_star_in, int64_t ldvs,
+                       double* mean_out, const GramCache* gc = nullptr, bool defer = false,
+                       const QuPre* pre = nullptr, const PredPrep* prep = nullptr,
+                       const double* xtr = nullptr);
+int64_t predict_mean_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d);
 void chains_smooth(gpar_ctx* c, int nchains, int64_t n, const double* t, const double* y,
                           int64_t ldy, const double* noise, int sdim,
                           const std::vector<ChainParamsHost>& cps, double* mean, double* var,

@@ -108,6 +108,7 @@ static constexpr Knob kKnobs[] = {
     {"gram_group", &gpar_ctx::gram_group, -1, 64, 0},
     {"fit_chunks", &gpar_ctx::fit_chunks, -1, 4096, 0},
     {"device_nm", &gpar_ctx::device_nm, 0, 1, 0},
+    {"chain_mean_first", &gpar_ctx::chain_mean_first, 0, 1, 0, true},
 };
 static const Knob* find_knob(const std::string& k) {
   for (const Knob& kn : kKnobs)

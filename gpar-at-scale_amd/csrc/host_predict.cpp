@@ -207,6 +207,45 @@ void path_samples(gpar_ctx* c, int sdim, const GainsOut& g, const ChainParamsHos
 }
 
 // --------------------------------------------------------------------------- prediction
+// A prediction's test inputs on the device, ascending: host inputs are stably sorted here (perm:
+// sorted position -> input position, empty when they were ascending already; the caller
+// un-permutes its outputs); device inputs must already be ascending and pass through.
+struct TestInputs {
+  const double *ts, *vs;
+  int64_t ldv;
+  std::vector<int64_t> perm;
+};
+static TestInputs stage_test_inputs(gpar_ctx* c, int mem, int64_t n_star, int64_t d,
+                                    const double* t_star_in, const double* v_star_in,
+                                    int64_t ldvs) {
+  TestInputs ti{t_star_in, v_star_in, ldvs, {}};
+  if (mem != GPAR_MEM_HOST) return ti;
+  std::vector<int64_t>& perm = ti.perm;
+  double* dts = ws<double>(c, "pr_ts", n_star);
+  double* dvs = ws<double>(c, "pr_vs", (size_t)n_star * d);
+  if (std::is_sorted(t_star_in, t_star_in + n_star)) {   // already ascending: no permutation
+    h2d(c, dts, t_star_in, n_star);
+    h2d_rows(c, dvs, v_star_in, ldvs, d, n_star);
+  } else {
+    perm.resize(n_star);
+    for (int64_t i = 0; i < n_star; ++i) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(),
+                     [&](int64_t a, int64_t b) { return t_star_in[a] < t_star_in[b]; });
+    std::vector<double> tsh(n_star), vsh((size_t)n_star * d);
+    for (int64_t i = 0; i < n_star; ++i) {
+      tsh[i] = t_star_in[perm[i]];
+      for (int64_t q = 0; q < d; ++q) vsh[i * d + q] = v_star_in[perm[i] * ldvs + q];
+    }
+    h2d(c, dts, tsh.data(), n_star);
+    h2d(c, dvs, vsh.data(), (size_t)n_star * d);
+  }
+  sync(c);
+  ti.ts = dts;
+  ti.vs = dvs;
+  ti.ldv = d;
+  return ti;
+}
+
 // Prediction half of get_gpar_scaled_predictions (gpar_scaled_inference.jl:63-135); see the
 // header of k_predict.hip for the algebra.
 // defer (device memory only): the outputs are queued on c->stream but not waited for -- the caller
@@ -220,36 +259,12 @@ void predict_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem,
   if (mode == GPAR_PREDICT_PATH)   // path draw (s, k, i): counter index k (sdim + 1) + i, 32 bits
     ARGCHECK((n + n_star) * (P.sdim + 1) <= ((int64_t)1 << 32),
              "path mode: (n + n_star) * (state dimension + 1) must be <= 2^32");
-  // ---- test inputs on device, ascending (host inputs are stably sorted here, outputs
-  //      un-permuted at the end; device inputs must already be ascending)
-  std::vector<int64_t> perm;
-  const double* ts = t_star_in;
-  const double* vs = v_star_in;
-  int64_t ldv_s = ldvs;
-  if (mem == GPAR_MEM_HOST) {
-    double* dts = ws<double>(c, "pr_ts", n_star);
-    double* dvs = ws<double>(c, "pr_vs", (size_t)n_star * d);
-    if (std::is_sorted(t_star_in, t_star_in + n_star)) {   // already ascending: no permutation
-      h2d(c, dts, t_star_in, n_star);
-      h2d_rows(c, dvs, v_star_in, ldvs, d, n_star);
-    } else {
-      perm.resize(n_star);
-      for (int64_t i = 0; i < n_star; ++i) perm[i] = i;
-      std::stable_sort(perm.begin(), perm.end(),
-                       [&](int64_t a, int64_t b) { return t_star_in[a] < t_star_in[b]; });
-      std::vector<double> tsh(n_star), vsh((size_t)n_star * d);
-      for (int64_t i = 0; i < n_star; ++i) {
-        tsh[i] = t_star_in[perm[i]];
-        for (int64_t q = 0; q < d; ++q) vsh[i * d + q] = v_star_in[perm[i] * ldvs + q];
-      }
-      h2d(c, dts, tsh.data(), n_star);
-      h2d(c, dvs, vsh.data(), (size_t)n_star * d);
-    }
-    sync(c);
-    ts = dts;
-    vs = dvs;
-    ldv_s = d;
-  }
+  // ---- test inputs on device, ascending
+  TestInputs ti = stage_test_inputs(c, mem, n_star, d, t_star_in, v_star_in, ldvs);
+  const std::vector<int64_t>& perm = ti.perm;
+  const double* ts = ti.ts;
+  const double* vs = ti.vs;
+  const int64_t ldv_s = ti.ldv;
   // ---- q(u): m_e, L_u = chol(Cuu), L_D = chol(D); w = L_u^{-T} m_e, X1 = L_u^{-1} and
   //      V = L_D^{-1} L_u^{-1} by substitution (noise-free Cuu: see run_q_u) -- or all of it
   //      precomputed for a batch of outputs (run_q_u_batch)
@@ -470,6 +485,117 @@ outputs:
   }
 }
 
+// --------------------------------------------------------------------------- mean-only prediction
+// The ANALYTIC mean alone (gpar_scaled_inference.jl:91-97 with e = m_e): with w = U_u^{-1} m_e,
+//   f = Cf*u w on the merged grid,  mean_i = f_k + (S (y* - f))_k,  k = pos[i],
+// one Kfu-vector product (launch_kfu_gemv, Kfu never stored) and the smoother on ONE column --
+// predict_impl whitens and adjoints all m columns of Cf*u to get the same number.  The training
+// rows of y* - f depend on the posterior only (xtr).
+void kfu_train_residual(gpar_ctx* c, const DevProblem& P, const Theta& th, const double* w,
+                        double* xtr) {
+  launch_kfu_gemv(c->stream, P.ok, P.v, P.ldv, P.n, P.z, P.ldz, P.m, (int)P.d, P.zc, w,
+                  1.0 / th.l_o, th.sv_o * th.sv_o, P.y, 1.0, nullptr, xtr, nullptr);
+  check_launch("predict mean: train f");
+}
+
+int64_t predict_mean_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d) {
+  const int64_t nt = n + n_star, nch = (nt + kChunk - 1) / kChunk;
+  const int64_t doubles = nt * (20 + 8 + 5)      // gains records, fix-up rows, grid, x and u
+                          + n + n_star * (4 + d)   // train residual, f*, mean, positions, sorted inputs
+                          + 4 * nch * 4            // carries
+                          + 8 * mp * mp;           // q(u) dense (no precomputed q(u))
+  return doubles * (int64_t)sizeof(double);
+}
+
+void predict_mean_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem, int64_t n_star,
+                       const double* t_star_in, const double* v_star_in, int64_t ldvs,
+                       double* mean_out, const GramCache* gc, bool defer, const QuPre* pre,
+                       const PredPrep* prep, const double* xtr) {
+  const int64_t n = P.n, m = P.m, d = P.d;
+  Timed tm_all(c, "pred_mean");
+  TestInputs ti = stage_test_inputs(c, mem, n_star, d, t_star_in, v_star_in, ldvs);
+  // ---- w = L_u^{-T} m_e: precomputed (run_q_u_batch), or q(u) here as predict_impl runs it
+  const double* w;
+  if (pre) {
+    w = pre->w;
+  } else {
+    QuOut q = run_q_u(c, P, th, gc);
+    double* wv = ws<double>(c, "pr_w", q.ld);
+    TrsvJobHost tv{ws<double>(c, "Kuu", 1), q.ld, (int)m, q.me, wv, 1};
+    auto* dtv = ws<TrsvJobHost>(c, "pr_trsv", 1);
+    h2d(c, dtv, &tv, 1);
+    launch_trsv(c->stream, dtv, 1);
+    check_launch("predict mean: w");
+    w = wv;
+  }
+  // ---- the training rows of x = y* - f
+  if (!xtr) {
+    double* xv = ws<double>(c, "pm_xtr", n);
+    kfu_train_residual(c, P, th, w, xv);
+    xtr = xv;
+  }
+  // ---- merged grid: times, noise, and x (train rows placed by the merge, test rows by the
+  //      test side's product below); no merged inputs
+  const int64_t nt = n + n_star;
+  const int64_t nch = (nt + kChunk - 1) / kChunk;
+  double* tm = ws<double>(c, "pm_tm", nt);
+  double* x = ws<double>(c, "pm_x", nt);
+  double* rm = ws<double>(c, "pm_rm", nt);
+  int64_t* pos = ws<int64_t>(c, "pm_pos", n_star);
+  double* fstar = ws<double>(c, "pm_fstar", n_star);
+  const double s2 = th.sigma * th.sigma;
+  launch_merge_side(c->stream, P.t, n, ti.ts, n_star, 0, xtr, s2, nullptr, 0, 0, tm, x, rm, nullptr,
+                    0, nullptr);
+  launch_merge_side(c->stream, ti.ts, n_star, P.t, n, 1, nullptr, 1e10, nullptr, 0, 0, tm, x, rm,
+                    nullptr, 0, pos);
+  check_launch("predict mean: merge");
+  {   // flops of the test side's distances and product; its n* m kernel evaluations come on top
+    Timed tm_(c, "pred_mean_kfu", 2.0 * (double)n_star * (double)m * (double)(d + 1));
+    launch_kfu_gemv(c->stream, P.ok, ti.vs, ti.ldv, n_star, P.z, P.ldz, m, (int)d, P.zc, w,
+                    1.0 / th.l_o, th.sv_o * th.sv_o, nullptr, 0.0, pos, x, fstar);
+  }
+  check_launch("predict mean: test f");
+  // ---- gains on the merged grid (noise sigma^2 train / 1e10 test), or the prepared ones
+  std::vector<ChainParamsHost> cps{chain_params_of(th, s2)};
+  GainsOut g;
+  if (prep) {
+    HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_prep_ready[prep - c->prep.data()], 0));
+    g = prep->g;
+  } else {
+    g = run_gains(c, P.sdim, tm, nt, cps, rm, false, "pmean");
+  }
+  // ---- S x at the test rows: whitening, carry, adjoint, reverse carry, all on one column
+  double* u = ws<double>(c, "pm_u", nt);
+  double* send = ws<double>(c, "pm_send", (size_t)nch * 4);
+  double* cin = ws<double>(c, "pm_cin", (size_t)nch * 4);
+  double* bend = ws<double>(c, "pm_bend", (size_t)nch * 4);
+  double* chat = ws<double>(c, "pm_chat", (size_t)nch * 4);
+  double* h = prep ? prep->h : ws<double>(c, "pm_h", (size_t)nt * 4);
+  double* dmean = ws<double>(c, "pm_mean", n_star);
+  launch_whiten_vec(c->stream, P.sdim, g.rec, 0, x, 0, nt, kChunk, nch, 1, u, 0, send, 0, 1, 0);
+  run_carry(c, P.sdim, g.phi, 0, send, cin, 0, nch, 1, 1, 1, "pmeanf");
+  if (!prep) launch_gains_adjoint(c->stream, P.sdim, g.rec, nt, kChunk, nch, 1, h);
+  launch_adjoint_local(c->stream, P.sdim, u, 1, 1, g.rec, g.g, cin, 1, nt, kChunk, nch, bend);
+  run_carry(c, P.sdim, g.phi, 0, bend, chat, 0, nch, 1, 1, 1, "pmeanb", /*rev=*/true);
+  launch_mean_finish(c->stream, P.sdim, u, h, chat, x, rm, fstar, pos, n_star, kChunk, dmean);
+  check_launch("predict mean: smoother");
+  // the prepared slot may be refilled once this prediction has read it
+  if (prep) HIPCHECK(hipEventRecord(c->ev_prep_free[prep - c->prep.data()], c->stream));
+  // ---- output
+  if (mem == GPAR_MEM_DEVICE) {
+    HIPCHECK(hipMemcpyAsync(mean_out, dmean, n_star * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (!defer) sync(c);
+  } else if (ti.perm.empty()) {
+    d2h(c, mean_out, dmean, n_star);
+    sync(c);
+  } else {
+    std::vector<double> hm(n_star);
+    d2h(c, hm.data(), dmean, n_star);
+    sync(c);
+    for (int64_t i = 0; i < n_star; ++i) mean_out[ti.perm[i]] = hm[i];
+  }
+}
+
 // get_gpar_scaled_predictions for a batch: batched fit, then each output's prediction at its
 // fitted theta (in output order).  chain (optional): after output i's prediction its mean is also
 // written to column chain_col[i] of chain (point k at chain[k * ld_chain + col]), so later outputs'
@@ -525,8 +651,17 @@ static void fit_predict_impl(gpar_ctx* ctx, const gpar_problem* probs, int32_t n
     stage_bytes = 8 * n_star * (1 + 2 * (int64_t)nprob);
     for (int i = 0; i < nprob; ++i) stage_bytes += 8 * n_star * ldvs[i];   // upper bound
   }
+  // "chain_mean_first": the chain carries means only (GPAR_scaled_examples.jl:172), so the
+  // context stream runs each output's mean-only prediction in chain order and the full
+  // prediction of output i, which supplies its std, follows on the side stream's lane
+  const bool mean_first = ctx->chain_mean_first && chain && mem == GPAR_MEM_DEVICE &&
+                          mode == GPAR_PREDICT_ANALYTIC;
+  int64_t mean_bytes = 0;
+  if (mean_first)
+    for (const auto& p : P)
+      mean_bytes = std::max(mean_bytes, predict_mean_ws_estimate(p.n, n_star, p.mp, p.d));
   fit_impl(ctx, P, log_theta0, o, theta_out, nlml_out, evals_out, &keep,
-           (lanes ? 2 : 1) * pred_bytes + stage_bytes);
+           (lanes ? 2 : 1) * pred_bytes + stage_bytes + mean_bytes);
   std::vector<int64_t> perm;
   std::vector<const double*> vs_dev(nprob, nullptr);
   std::vector<int64_t> lds_dev(nprob, 0);
@@ -616,7 +751,34 @@ static void fit_predict_impl(gpar_ctx* ctx, const gpar_problem* probs, int32_t n
     HIPCHECK(hipEventRecord(ctx->ev_fork, ctx->main));
     HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
   }
-  for (int i = 0; i < nprob; ++i) {
+  for (int i = 0; i < nprob && mean_first; ++i) {
+    const double* q = theta_out + 5 * i;
+    const Theta th{q[0], q[1], q[2], q[3], q[4]};
+    const GramCache* gc = keep.valid[i] ? &keep.gram[i] : nullptr;
+    const QuPre* pq = pre.empty() ? nullptr : &pre[i];
+    {   // ordered part: the mean, its chain column, the event the full prediction follows
+      LaneScope lane_(ctx, 0);
+      predict_mean_impl(ctx, P[i], th, mem, n_star, t_star, v_star[i], ldvs[i], mean_out[i], gc,
+                        /*defer=*/true, pq);
+      if (chain_col[i] >= 0)
+        HIPCHECK(hipMemcpy2DAsync(chain + chain_col[i], ld_chain * sizeof(double), mean_out[i],
+                                  sizeof(double), sizeof(double), n_star, hipMemcpyDeviceToDevice,
+                                  ctx->stream));
+      HIPCHECK(hipEventRecord(ctx->ev_fork, ctx->main));
+    }
+    {   // output i's std, beside the later outputs' means; its mean goes to a scratch vector
+      LaneScope lane_(ctx, 1);
+      HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+      double* mean_full = ws<double>(ctx, "fp_mean_full", n_star);
+      predict_impl(ctx, P[i], th, mem, n_star, t_star, v_star[i], ldvs[i], mode, samples,
+                   seed + (uint64_t)i, mean_full, std_out[i], gc, /*defer=*/true, pq);
+    }
+  }
+  if (mean_first) {
+    HIPCHECK(hipEventRecord(ctx->ev_join, ctx->side));
+    HIPCHECK(hipStreamWaitEvent(ctx->main, ctx->ev_join, 0));
+  }
+  for (int i = 0; i < nprob && !mean_first; ++i) {
     const double* q = theta_out + 5 * i;
     const Theta th{q[0], q[1], q[2], q[3], q[4]};
     LaneScope lane_(ctx, lanes ? (i & 1) : 0);
@@ -734,6 +896,19 @@ int32_t gpar_predict(gpar_ctx* ctx, const gpar_problem* prob, const double* thet
   API_END(ctx)
 }
 
+int32_t gpar_predict_mean(gpar_ctx* ctx, const gpar_problem* prob, const double* theta,
+                          int64_t n_star, const double* t_star, const double* v_star,
+                          int64_t ldvs, double* mean) {
+  API_BEGIN(ctx)
+  ARGCHECK(prob && theta && t_star && v_star && mean, "null argument");
+  ARGCHECK(n_star >= 1, "n_star must be >= 1");
+  ARGCHECK(ldvs >= prob->d, "ldvs must be >= d");
+  DevProblem P = prepare_problem(ctx, *prob, 0);
+  std::vector<Theta> th = thetas_from(theta, 1);
+  predict_mean_impl(ctx, P, th[0], prob->mem, n_star, t_star, v_star, ldvs, mean);
+  API_END(ctx)
+}
+
 int32_t gpar_mc_normals(gpar_ctx* ctx, int32_t samples, int64_t m, uint64_t seed, double* xi_out) {
   API_BEGIN(ctx)
   ARGCHECK(xi_out, "null argument");
@@ -815,18 +990,25 @@ struct gpar_posterior {
     gpar::DevProblem p;        // t, v, z, y: borrowed (device problems) or owned (host problems)
     gpar::Theta th;
     gpar::QuPre q;             // me, w, X1, Vm, cov in owned device memory
+    // the mean-only prediction's training rows y - Kfu w (n doubles, owned), filled on first use
+    // (post_xtr); xtr_ev: recorded behind the fill when it ran on the side stream
+    // (gpar_posterior_prepare_mean), and waited for by every reader on the context stream
+    mutable const double* xtr = nullptr;
+    mutable hipEvent_t xtr_ev = nullptr;
   };
   std::vector<Out> outs;
-  std::vector<void*> owned;    // hipMalloc'd blocks, freed by gpar_posterior_destroy
+  mutable std::vector<void*> owned;   // hipMalloc'd blocks, freed by gpar_posterior_destroy
   ~gpar_posterior() {
     (void)hipSetDevice(device);
+    for (const Out& o : outs)
+      if (o.xtr_ev) (void)hipEventDestroy(o.xtr_ev);
     for (void* b : owned) (void)hipFree(b);
   }
 };
 
 namespace gpar {
 
-static double* post_alloc(gpar_posterior* post, size_t doubles) {
+static double* post_alloc(const gpar_posterior* post, size_t doubles) {
   void* b = nullptr;
   const hipError_t e = hipMalloc(&b, std::max<size_t>(doubles, 1) * sizeof(double));
   if (e != hipSuccess) {
@@ -843,6 +1025,83 @@ static const double* post_keep(gpar_ctx* c, gpar_posterior* post, const double* 
   double* dst = post_alloc(post, doubles);
   HIPCHECK(hipMemcpyAsync(dst, src, doubles * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return dst;
+}
+
+// Output i's training rows y - Kfu w of the mean-only prediction, computed on c->stream on first
+// use and kept by the posterior (the same kernel either way: a later call finds the bits it would
+// have computed).  on_side: c->stream is the side stream, so an event orders the readers.
+static const double* post_xtr(gpar_ctx* c, const gpar_posterior* post, int i, bool on_side) {
+  const gpar_posterior::Out& o = post->outs[i];
+  if (o.xtr) return o.xtr;
+  double* x = post_alloc(post, o.p.n);
+  kfu_train_residual(c, o.p, o.th, o.q.w, x);
+  if (on_side) {
+    if (!o.xtr_ev) HIPCHECK(hipEventCreateWithFlags(&o.xtr_ev, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(o.xtr_ev, c->stream));
+  }
+  o.xtr = x;
+  return x;
+}
+
+// What gpar_posterior_prepare queues on the side stream for output i and test times t_star (the
+// merged grid's gains and fix-up rows into the next of the context's two slots); with_f: also
+// the output's training rows of the mean-only prediction, if the posterior has none yet.
+static void posterior_prepare(gpar_ctx* ctx, const gpar_posterior* post, int32_t i, int64_t n_star,
+                              const double* t_star, bool with_f) {
+  const gpar_posterior::Out& o = post->outs[i];
+  const DevProblem& P = o.p;
+  if (ctx->prep.empty()) ctx->prep.resize(2);
+  for (int k = 0; k < 2; ++k)
+    for (hipEvent_t* ev : {&ctx->ev_prep_ready[k], &ctx->ev_prep_free[k]})
+      if (!*ev) HIPCHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  const int slot = ctx->prep_next;
+  ctx->prep_next ^= 1;
+  PredPrep& s = ctx->prep[slot];
+  s.valid = false;
+  // the side stream follows the context stream (inputs, earlier calls) and the slot's last reader
+  HIPCHECK(hipEventRecord(ctx->ev_fork, ctx->main));
+  HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+  HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_prep_free[slot], 0));
+  const std::string tag = "prep" + std::to_string(slot);
+  const int64_t nt = P.n + n_star;
+  const int64_t nch = (nt + kChunk - 1) / kChunk;
+  {
+    OnStream on_(ctx, ctx->side);
+    if (with_f) post_xtr(ctx, post, i, /*on_side=*/true);
+    // the merged grid's times and noise (predict_impl merges the inputs again, identically)
+    double* tm = ws<double>(ctx, tag + "_tm", nt);
+    double* ym = ws<double>(ctx, tag + "_ym", nt);
+    double* rm = ws<double>(ctx, tag + "_rm", nt);
+    const double s2 = o.th.sigma * o.th.sigma;
+    launch_merge_side(ctx->stream, P.t, P.n, t_star, n_star, 0, P.y, s2, nullptr, 0, 0, tm, ym, rm,
+                      nullptr, 0, nullptr);
+    launch_merge_side(ctx->stream, t_star, n_star, P.t, P.n, 1, nullptr, 1e10, nullptr, 0, 0, tm, ym,
+                      rm, nullptr, 0, nullptr);
+    check_launch("prepare: merge");
+    std::vector<ChainParamsHost> cps{chain_params_of(o.th, s2)};
+    s.g = run_gains(ctx, P.sdim, tm, nt, cps, rm, false, tag);
+    s.h = ws<double>(ctx, tag + "_h", (size_t)nt * 4);
+    launch_gains_adjoint(ctx->stream, P.sdim, s.g.rec, nt, kChunk, nch, 1, s.h);
+    check_launch("prepare: gains");
+    HIPCHECK(hipEventRecord(ctx->ev_prep_ready[slot], ctx->side));
+  }
+  s.post_id = post->id;
+  s.out = i;
+  s.ts = t_star;
+  s.n_star = n_star;
+  s.valid = true;
+}
+
+// the slot gpar_posterior_prepare[_mean] filled for this output and these test times, taken
+static const PredPrep* take_prep(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                 int64_t n_star, const double* t_star) {
+  const PredPrep* prep = nullptr;
+  for (PredPrep& s : ctx->prep)
+    if (s.valid && s.post_id == post->id && s.out == i && s.ts == t_star && s.n_star == n_star) {
+      s.valid = false;
+      prep = &s;
+    }
+  return prep;
 }
 
 }  // namespace gpar
@@ -943,47 +1202,37 @@ int32_t gpar_posterior_prepare(gpar_ctx* ctx, const gpar_posterior* post, int32_
   ARGCHECK(post->mem == GPAR_MEM_DEVICE, "gpar_posterior_prepare: device-memory posteriors only");
   ARGCHECK(i >= 0 && i < (int32_t)post->outs.size(), "output index out of range");
   ARGCHECK(n_star >= 1, "n_star must be >= 1");
+  posterior_prepare(ctx, post, i, n_star, t_star, /*with_f=*/false);
+  API_END(ctx)
+}
+
+int32_t gpar_posterior_prepare_mean(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                    int64_t n_star, const double* t_star) {
+  API_BEGIN(ctx)
+  ARGCHECK(post && t_star, "null argument");
+  ARGCHECK(post->device == ctx->device, "the posterior belongs to another device's context");
+  ARGCHECK(post->mem == GPAR_MEM_DEVICE, "gpar_posterior_prepare_mean: device-memory posteriors only");
+  ARGCHECK(i >= 0 && i < (int32_t)post->outs.size(), "output index out of range");
+  ARGCHECK(n_star >= 1, "n_star must be >= 1");
+  posterior_prepare(ctx, post, i, n_star, t_star, /*with_f=*/true);
+  API_END(ctx)
+}
+
+int32_t gpar_posterior_predict_mean(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                    int64_t n_star, const double* t_star, const double* v_star,
+                                    int64_t ldvs, double* mean) {
+  API_BEGIN(ctx)
+  ARGCHECK(post && t_star && v_star && mean, "null argument");
+  ARGCHECK(post->device == ctx->device, "the posterior belongs to another device's context");
+  ARGCHECK(i >= 0 && i < (int32_t)post->outs.size(), "output index out of range");
   const gpar_posterior::Out& o = post->outs[i];
-  const DevProblem& P = o.p;
-  if (ctx->prep.empty()) ctx->prep.resize(2);
-  for (int k = 0; k < 2; ++k)
-    for (hipEvent_t* ev : {&ctx->ev_prep_ready[k], &ctx->ev_prep_free[k]})
-      if (!*ev) HIPCHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-  const int slot = ctx->prep_next;
-  ctx->prep_next ^= 1;
-  PredPrep& s = ctx->prep[slot];
-  s.valid = false;
-  // the side stream follows the context stream (inputs, earlier calls) and the slot's last reader
-  HIPCHECK(hipEventRecord(ctx->ev_fork, ctx->main));
-  HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-  HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_prep_free[slot], 0));
-  const std::string tag = "prep" + std::to_string(slot);
-  const int64_t nt = P.n + n_star;
-  const int64_t nch = (nt + kChunk - 1) / kChunk;
-  {
-    OnStream on_(ctx, ctx->side);
-    // the merged grid's times and noise (predict_impl merges the inputs again, identically)
-    double* tm = ws<double>(ctx, tag + "_tm", nt);
-    double* ym = ws<double>(ctx, tag + "_ym", nt);
-    double* rm = ws<double>(ctx, tag + "_rm", nt);
-    const double s2 = o.th.sigma * o.th.sigma;
-    launch_merge_side(ctx->stream, P.t, P.n, t_star, n_star, 0, P.y, s2, nullptr, 0, 0, tm, ym, rm,
-                      nullptr, 0, nullptr);
-    launch_merge_side(ctx->stream, t_star, n_star, P.t, P.n, 1, nullptr, 1e10, nullptr, 0, 0, tm, ym,
-                      rm, nullptr, 0, nullptr);
-    check_launch("prepare: merge");
-    std::vector<ChainParamsHost> cps{chain_params_of(o.th, s2)};
-    s.g = run_gains(ctx, P.sdim, tm, nt, cps, rm, false, tag);
-    s.h = ws<double>(ctx, tag + "_h", (size_t)nt * 4);
-    launch_gains_adjoint(ctx->stream, P.sdim, s.g.rec, nt, kChunk, nch, 1, s.h);
-    check_launch("prepare: gains");
-    HIPCHECK(hipEventRecord(ctx->ev_prep_ready[slot], ctx->side));
-  }
-  s.post_id = post->id;
-  s.out = i;
-  s.ts = t_star;
-  s.n_star = n_star;
-  s.valid = true;
+  ARGCHECK(n_star >= 1, "n_star must be >= 1");
+  ARGCHECK(ldvs >= o.p.d, "ldvs must be >= d");
+  const PredPrep* prep = take_prep(ctx, post, i, n_star, t_star);
+  const double* xtr = post_xtr(ctx, post, i, /*on_side=*/false);
+  if (o.xtr_ev) HIPCHECK(hipStreamWaitEvent(ctx->stream, o.xtr_ev, 0));
+  predict_mean_impl(ctx, o.p, o.th, post->mem, n_star, t_star, v_star, ldvs, mean, nullptr, false,
+                    &o.q, prep, xtr);
   API_END(ctx)
 }
 
@@ -1002,13 +1251,7 @@ int32_t gpar_posterior_predict(gpar_ctx* ctx, const gpar_posterior* post, int32_
            "bad mode");
   if (mode != GPAR_PREDICT_ANALYTIC)
     ARGCHECK(samples >= 2 && samples <= kMaxSamples, "MC / path modes take 2..65536 samples");
-  // a slot gpar_posterior_prepare filled for this output and these test times
-  const PredPrep* prep = nullptr;
-  for (PredPrep& s : ctx->prep)
-    if (s.valid && s.post_id == post->id && s.out == i && s.ts == t_star && s.n_star == n_star) {
-      s.valid = false;
-      prep = &s;
-    }
+  const PredPrep* prep = take_prep(ctx, post, i, n_star, t_star);
   predict_impl(ctx, o.p, o.th, post->mem, n_star, t_star, v_star, ldvs, mode, samples, seed, mean,
                std, nullptr, false, &o.q, prep);
   API_END(ctx)

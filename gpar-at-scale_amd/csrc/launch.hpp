@@ -286,6 +286,22 @@ void launch_scatter_chains(hipStream_t st, const double* src, int64_t lds, int64
 void launch_gather_chains(hipStream_t st, const double* src, int64_t lds, int64_t ns,
                           const int64_t* pos, double* dst, int64_t ldd, int nchains);
 
+// k_kfu_gemv.hip (the mean-only prediction)
+// f_k = sum_c s_o kappa(|v_k - z_c| / l_o) w_c for k < n, Kfu evaluated on the fly (any d; smooth
+// kernels: MFMA Gram form with the centres zc; Matern-1/2: direct differences): fout[k] = f_k and
+// xout[dst(k)] = a_y y[k] - f_k, dst(k) = pos ? pos[k] : k (fout, xout, y, pos optional; y null: 0).
+// Deterministic: a row's value does not depend on n or the grid.
+void launch_kfu_gemv(hipStream_t st, int out_kind, const double* v, int64_t ldv, int64_t n,
+                     const double* z, int64_t ldz, int64_t m, int d, const double* zc,
+                     const double* w, double inv_lo, double s_o, const double* y, double a_y,
+                     const int64_t* pos, double* xout, double* fout);
+// mean[i] = fstar[i] + x[k] - rm[k] (u[k] + h_k . chat_{chunk(k)}), k = pos[i]: the smoothed
+// single column x at the test rows (u: launch_adjoint_local's one-column output)
+void launch_mean_finish(hipStream_t st, int sdim, const double* u, const double* h,
+                        const double* chat, const double* x, const double* rm,
+                        const double* fstar, const int64_t* pos, int64_t nstar, int L,
+                        double* mean);
+
 // k_path.hip (posterior path sampling: the simulation smoother batched over samples; layouts in
 // the file header)
 void launch_kfu_from_dist(hipStream_t st, int out_kind, double* K, int64_t n, int64_t m,

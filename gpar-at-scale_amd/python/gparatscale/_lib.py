@@ -28,6 +28,7 @@ EXPORTED = (
     "gpar_ctx_set_lanes", "gpar_ctx_set_cu_split", "gpar_ctx_set_fit_overlap", "gpar_ctx_get_cu_split", "gpar_ctx_set_dist_cache", "gpar_ctx_set_dist_cache_keep", "gpar_ctx_dist_cache_stats",
     "gpar_pairwise_distances", "gpar_ctx_set_predict_fused", "gpar_ctx_set_input_stream", "gpar_ctx_set_schedule", "gpar_ctx_get_schedule",
     "gpar_fit_posterior", "gpar_posterior_predict", "gpar_posterior_prepare", "gpar_posterior_destroy",
+    "gpar_predict_mean", "gpar_posterior_predict_mean", "gpar_posterior_prepare_mean",
     "gpar_nm_create", "gpar_nm_destroy", "gpar_nm_ask", "gpar_nm_tell", "gpar_nm_result",
 )
 
@@ -124,6 +125,9 @@ def load(path: str | None = None):
                                              vp, vp]),
             "gpar_posterior_prepare": (i32, [vp, vp, i32, i64, vp]),
             "gpar_posterior_destroy": (i32, [vp]),
+            "gpar_predict_mean": (i32, [vp, C.POINTER(GparProblem), dp, i64, dp, dp, i64, dp]),
+            "gpar_posterior_predict_mean": (i32, [vp, vp, i32, i64, vp, vp, i64, vp]),
+            "gpar_posterior_prepare_mean": (i32, [vp, vp, i32, i64, vp]),
             "gpar_mc_normals": (i32, [vp, i32, i64, C.c_uint64, dp]),
             "gpar_path_normals": (i32, [vp, i32, i64, i32, C.c_uint64, dp]),
             "gpar_lgssm_posterior_rand": (i32, [vp, i64, dp, dp, dp, i32, dp, i32, C.c_uint64, i32, dp]),
@@ -145,9 +149,11 @@ def load(path: str | None = None):
             "gpar_nm_tell": (i32, [vp, C.c_double]),
             "gpar_nm_result": (i32, [vp, dp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32)]),
         })
+        later = ("gpar_debug_counter", "gpar_predict_mean", "gpar_posterior_predict_mean",
+                 "gpar_posterior_prepare_mean")
         for name, (res, args) in sig.items():
-            if name == "gpar_debug_counter" and not hasattr(lib, name):
-                continue   # a diagnostic only: older builds (library A/B runs) lack it
+            if name in later and not hasattr(lib, name):
+                continue   # older builds (library A/B runs, tools/lib_bitcheck.py) lack these
             f = getattr(lib, name)
             f.restype = res
             f.argtypes = args
@@ -284,10 +290,10 @@ class Context:
     def set_schedule(self, knob, value):
         """A schedule knob (gpar_ctx_set_schedule: overlap, overlap_group, qu_batch, dense_early,
         post_gram, compact_rec, predict_lanes, serialize, predict_fused, dg_rows_w, gram_group,
-        scaled_gram, fit_chunks, device_nm; the header lists their values); results are
-        bit-identical with any setting except the plan knobs predict_fused, dg_rows_w, gram_group
-        and scaled_gram (last bits)
-        and device_nm (the device's exp() in the chains fit's parameters)."""
+        scaled_gram, fit_chunks, device_nm, chain_mean_first; the header lists their values);
+        results are bit-identical with any setting except the plan knobs predict_fused, dg_rows_w,
+        gram_group and scaled_gram (last bits), device_nm (the device's exp() in the chains fit's
+        parameters) and chain_mean_first (a chained call's means come from the mean-only path)."""
         self.check(load().gpar_ctx_set_schedule(self.h, knob.encode(), int(value)))
 
     def schedule(self, knob):

@@ -497,12 +497,50 @@ class Posterior:
                                              ldvs, md, int(samples), int(seed), _ptr(mean), _ptr(std)))
         return mean, std
 
+    def predict_mean(self, i, t_star, V_star):
+        """Output i's analytic mean alone at (t_star, V_star) (gpar_posterior_predict_mean): the
+        quantity a chained sweep passes on, without the variance's work.  Tensors as predict's."""
+        if not 0 <= int(i) < len(self._problems):
+            raise _arg_error(f"output index {i} out of range (0..{len(self._problems) - 1})")
+        p = self._problems[i]
+        keep = _Keep()
+        ctx, lib = context(self.device), _lib.load()
+        if p.mem == _lib.GPAR_MEM_DEVICE:
+            import torch
+            vsp, ldvs, ns, ds = _dev_points(V_star, keep)
+            tsp = _dev_vec(t_star, keep)
+            if ns != t_star.numel() or ds != p.d:
+                raise _arg_error("inference inputs must be N* x D with N* = len(t_star)")
+            mean = torch.empty(ns, dtype=torch.float64, device=t_star.device)
+            with _after_torch(ctx):
+                ctx.check(lib.gpar_posterior_predict_mean(ctx.h, self.h, int(i), ns, tsp, vsp, ldvs,
+                                                          mean.data_ptr()))
+            # the prepared slot is consumed (stream-ordered before any later use of the memory)
+            self._prepared.pop(int(i), None)
+            return mean
+        vsp, ldvs, ns, ds = _host_points(V_star, keep)
+        if ds != p.d or ns != len(np.asarray(t_star)):
+            raise _arg_error("inference inputs must be D x N* with N* = len(t_star)")
+        mean = np.zeros(ns)
+        ctx.check(lib.gpar_posterior_predict_mean(ctx.h, self.h, int(i), ns,
+                                                  _host_vec(t_star, keep), vsp, ldvs, _ptr(mean)))
+        return mean
+
     def prepare(self, i, t_star):
         """Queue output i's inference-input-independent prediction work for device test times
         t_star (gpar_posterior_prepare) on the context's side stream; the next predict(i, t_star,
         ...) with the same tensor uses it.  Device problems only.  The queued kernels read t_star
         asynchronously, so it must be contiguous (no temporary copy) and must not be freed or
         written until that predict has run: the Posterior holds a reference to it until then."""
+        self._prepare(i, t_star, "gpar_posterior_prepare")
+
+    def prepare_mean(self, i, t_star):
+        """prepare, and also output i's training-side share of predict_mean if the posterior does
+        not hold it yet (gpar_posterior_prepare_mean).  The next predict_mean(i, t_star, ...) or
+        predict(i, t_star, ...) with the same tensor uses the slot; t_star as for prepare."""
+        self._prepare(i, t_star, "gpar_posterior_prepare_mean")
+
+    def _prepare(self, i, t_star, entry):
         if not 0 <= int(i) < len(self._problems):
             raise _arg_error(f"output index {i} out of range (0..{len(self._problems) - 1})")
         if self._problems[i].mem != _lib.GPAR_MEM_DEVICE:
@@ -512,8 +550,7 @@ class Posterior:
                              "kernels read it after this call returns)")
         ctx, lib = context(self.device), _lib.load()
         with _after_torch(ctx):
-            ctx.check(lib.gpar_posterior_prepare(ctx.h, self.h, int(i), t_star.numel(),
-                                                 t_star.data_ptr()))
+            ctx.check(getattr(lib, entry)(ctx.h, self.h, int(i), t_star.numel(), t_star.data_ptr()))
         # alive until the matching predict (two slots per context: at most two pending)
         self._prepared[int(i)] = t_star
         while len(self._prepared) > 2:
@@ -718,6 +755,38 @@ def predict_scaled(input_locations, pseudo_input_locations, time_loc, outputs, t
     ctx.check(lib.gpar_predict(ctx.h, C.byref(p), _ptr(th), ns, tsp, vsp, ldvs, md, int(samples),
                                int(seed), _ptr(mean), _ptr(std)))
     return mean, std
+
+
+def predict_mean_scaled(input_locations, pseudo_input_locations, time_loc, outputs, theta,
+                        inference_time_loc, inference_input_locations, out_kernel="matern52",
+                        time_kernel="matern52", device=0, qu_kuu_noise=False):
+    """The analytic mean of predict_scaled alone (gpar_predict_mean): what a chain of outputs
+    passes on (GPAR_scaled_examples.jl:172), at O((N + N*) M D) instead of O(N* M^2).  Returns the
+    mean at the inference locations, in their input order.  Not the "mc" / "path" sample means."""
+    p, keep = make_problem(input_locations, pseudo_input_locations, time_loc, outputs,
+                           out_kernel, time_kernel, qu_kuu_noise=qu_kuu_noise)
+    th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(5))
+    if p.mem == _lib.GPAR_MEM_DEVICE:
+        import torch
+        vsp, ldvs, ns, ds = _dev_points(inference_input_locations, keep)
+        tsp = _dev_vec(inference_time_loc, keep)
+        if ns != inference_time_loc.numel() or ds != p.d:
+            raise _arg_error("inference inputs must be N* x D with N* = len(inference_time_loc)")
+        ctx, lib = context(device), _lib.load()
+        mean = torch.empty(ns, dtype=torch.float64, device=inference_time_loc.device)
+        with _after_torch(ctx):
+            ctx.check(lib.gpar_predict_mean(ctx.h, C.byref(p), _ptr(th), ns, tsp, vsp, ldvs,
+                                            mean.data_ptr()))
+        return mean
+    vsp, ldvs, ns, ds = _host_points(inference_input_locations, keep)
+    tsp = _host_vec(inference_time_loc, keep)
+    if ds != p.d or ns != len(np.asarray(inference_time_loc)):
+        raise _arg_error("inference inputs must have the training dimension and one point per "
+                         "inference time")
+    ctx, lib = context(device), _lib.load()
+    mean = np.zeros(ns)
+    ctx.check(lib.gpar_predict_mean(ctx.h, C.byref(p), _ptr(th), ns, tsp, vsp, ldvs, _ptr(mean)))
+    return mean
 
 
 def get_gpar_scaled_predictions(input_locations, pseudo_input_locations, time_loc, outputs,

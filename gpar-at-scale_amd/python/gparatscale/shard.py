@@ -98,7 +98,7 @@ def owners_of(shards: list[list[int]]) -> dict[int, int]:
     return {p: r for r, owned in enumerate(shards) for p in owned}
 
 
-def chained_predictions(outputs, owners: dict, predict_fn, chain, prepare_fn=None):
+def chained_predictions(outputs, owners: dict, predict_fn, chain, prepare_fn=None, mean_fn=None):
     """Predictions with chained inference inputs across ranks (GPAR_scaled_examples.jl:172,
     eeg.jl:249,274: output p's inference inputs include the predicted means of earlier outputs).
 
@@ -111,7 +111,11 @@ def chained_predictions(outputs, owners: dict, predict_fn, chain, prepare_fn=Non
     prepare_fn(p) (optional, e.g. Posterior.prepare) queues the part of p's prediction that does
     not read the chain; each rank calls it for its next output before predicting the current one
     (and for its first output up front), so that part runs beside the sweep.
-    Returns {p: (mean, std)} for this rank's outputs."""
+    mean_fn(p, chain) -> mean (optional, e.g. Posterior.predict_mean with prepare_fn =
+    Posterior.prepare_mean): only means travel along the chain, so the ordered loop then calls
+    mean_fn instead of predict_fn and broadcasts that mean; the rank's predict_fn(p, chain) calls
+    run after the last broadcast, against the finished chain, and supply the stds.
+    Returns {p: (mean, std)} for this rank's outputs (with mean_fn: its mean, predict_fn's std)."""
     import torch
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -127,12 +131,19 @@ def chained_predictions(outputs, owners: dict, predict_fn, chain, prepare_fn=Non
         if owner == rank:
             if prepare_fn is not None and p in nxt:
                 prepare_fn(nxt[p])
-            mean, std = predict_fn(p, chain)
-            mine[p] = (mean, std)
+            if mean_fn is not None:
+                mean = mean_fn(p, chain)
+                mine[p] = mean
+            else:
+                mean, std = predict_fn(p, chain)
+                mine[p] = (mean, std)
             col.copy_(torch.as_tensor(mean, dtype=chain.dtype).to(chain.device))
         if on:
             dist.broadcast(col, owner)
         chain[:, p - 1].copy_(col)
+    if mean_fn is not None:   # the stds, off the ordered path
+        for p in own:
+            mine[p] = (mine[p], predict_fn(p, chain)[1])
     return mine
 
 
@@ -213,14 +224,17 @@ def assign_chained(P: int, world: int, fit_ms=None, sweep_ms: float = SWEEP_MS_P
     return owned
 
 
-def chained_sweep_blocks(shards, predict_fn, chain, prepare_fn=None, gather=True):
+def chained_sweep_blocks(shards, predict_fn, chain, prepare_fn=None, gather=True, mean_fn=None):
     """The chained sweep over contiguous blocks (assign_chained): each rank receives the earlier
     blocks' predicted means point to point from their owners, predicts its own block in order
     (predict_fn(p, chain) -> (mean, std), its next output prepared ahead with prepare_fn), and
     sends its block's means to every later rank.  No rank waits in a collective for a rank that is
     still fitting.  gather: at the end the last rank broadcasts the whole chain, so every rank
     holds every mean (as chained_predictions leaves it).  `chain` as chained_predictions'.
-    Returns {p: (mean, std)} for this rank's outputs."""
+    mean_fn(p, chain) -> mean (optional, as chained_predictions'): the block's ordered loop calls
+    it instead of predict_fn; the rank's predict_fn(p, chain) calls, which supply the stds, run
+    once the block's sends are posted, so the next owner starts while they run.
+    Returns {p: (mean, std)} for this rank's outputs (with mean_fn: its mean, predict_fn's std)."""
     import torch
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -251,8 +265,12 @@ def chained_sweep_blocks(shards, predict_fn, chain, prepare_fn=None, gather=True
     for i, p in enumerate(own):
         if prepare_fn is not None and i + 1 < len(own):
             prepare_fn(own[i + 1])
-        mean, std = predict_fn(p, chain)
-        mine[p] = (mean, std)
+        if mean_fn is not None:
+            mean = mean_fn(p, chain)
+            mine[p] = mean
+        else:
+            mean, std = predict_fn(p, chain)
+            mine[p] = (mean, std)
         chain[:, p - 1] = torch.as_tensor(mean, dtype=chain.dtype).to(chain.device)
     works = []
     if on and own:
@@ -260,6 +278,9 @@ def chained_sweep_blocks(shards, predict_fn, chain, prepare_fn=None, gather=True
         blk = blk.cpu() if host else blk
         for r in range(rank + 1, world):
             works.append(dist.isend(blk, dst=r))
+    if mean_fn is not None:   # the stds, behind the posted sends
+        for p in own:
+            mine[p] = (mine[p], predict_fn(p, chain)[1])
     for w in works:
         w.wait()
     if on and gather:

@@ -206,6 +206,15 @@ int32_t gpar_ctx_set_predict_fused(gpar_ctx* ctx, int32_t on);
  *                   the host after each round's values come back (0).  A fit with a wall-clock
  *                   time limit always runs on the host.  The same steps; the device's exp() in
  *                   the chain parameters may move a value in its last bit
+ *   "chain_mean_first" 1: gpar_fit_predict_chain with device-memory problems and
+ *                   GPAR_PREDICT_ANALYTIC runs, in chain order on the context stream, only each
+ *                   output's mean-only prediction (gpar_predict_mean's path) and the write of its
+ *                   chain column; output i's full prediction, which supplies std_out[i], follows
+ *                   that write on the side stream beside the later outputs' means.  mean_out[i]
+ *                   is then the mean-only mean (equal to the chain column bit for bit; within
+ *                   rounding of the full prediction's).  0 (default): the full prediction per
+ *                   output in chain order.  No effect on any other call, mode or memory space.
+ *                   Bit-identical to its serialized twin
  * The environment variable GPAR_<KNOB> (upper case) sets a knob at context creation.
  * GPAR_ERR_ARG for an unknown knob or value.  Every non-default value is a supported schedule
  * mode; the A/B-only knobs of round 4 (split_head, dg_share, tail_cus, predict_d2, dense_early 2)
@@ -298,6 +307,19 @@ int32_t gpar_predict(gpar_ctx* ctx, const gpar_problem* prob, const double* thet
                      int64_t n_star, const double* t_star, const double* v_star, int64_t ldvs,
                      int32_t mode, int32_t samples, uint64_t seed, double* mean, double* std);
 
+/* The ANALYTIC mean of gpar_predict without its variance (same arguments, no std).  Only means
+ * travel along a chain of outputs (examples/GPAR_scaled_examples.jl:172, examples/eeg.jl:249,274),
+ * and the mean needs Cf*u only through f = Cf*u U_u^{-1} m_e: one kernel-matrix--vector product
+ * with the kernel evaluated on the fly, then the smoother on the single column y* - f of the
+ * merged grid, mean_i = f_k + (S (y* - f))_k (gpar_scaled_inference.jl:91-97 with e = m_e).
+ * O((n + n_star) m d) work and O(n + n_star) workspace instead of gpar_predict's O(n_star m^2) and
+ * (n + n_star) x (Mp + 64); any d.  The same number as gpar_predict's ANALYTIC mean summed in
+ * another order (rounding apart).  The MC and PATH modes chain a SAMPLE mean over their draws,
+ * which this does not reproduce. */
+int32_t gpar_predict_mean(gpar_ctx* ctx, const gpar_problem* prob, const double* theta,
+                          int64_t n_star, const double* t_star, const double* v_star,
+                          int64_t ldvs, double* mean);
+
 /* The standard-normal draws MC mode uses for (samples, m, seed): xi_out[s*m + j] is the j-th
  * coordinate of draw s (host, samples x m).  The m_e sample of draw s is m_e + chol(inv(D)).L
  * xi_s, as Distributions' rand(MvNormal(m_e, Symmetric(inv(D)))) maps a standard-normal vector
@@ -381,6 +403,20 @@ int32_t gpar_posterior_predict(gpar_ctx* ctx, const gpar_posterior* post, int32_
  * posterior's identity, not its address: a slot left by a destroyed posterior is never used. */
 int32_t gpar_posterior_prepare(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
                                int64_t n_star, const double* t_star);
+/* gpar_predict_mean from a posterior object: output i's ANALYTIC mean alone (not the MC / PATH
+ * sample means), for a chained sweep whose ordered part needs nothing else.  The training rows of
+ * y* - f (n doubles) depend on the posterior only: they are computed on first use per output and
+ * kept in posterior-owned memory until gpar_posterior_destroy; a call that finds them returns the
+ * same bits as the call that computed them.  Uses a matching slot of gpar_posterior_prepare or
+ * gpar_posterior_prepare_mean if there is one (and consumes it), with bit-identical results. */
+int32_t gpar_posterior_predict_mean(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                    int64_t n_star, const double* t_star, const double* v_star,
+                                    int64_t ldvs, double* mean);
+/* gpar_posterior_prepare, and also output i's training rows for gpar_posterior_predict_mean if
+ * the posterior does not hold them yet, all on the side stream.  The same two slots, matching
+ * rules and t_star lifetime rule; either predict call may consume the slot. */
+int32_t gpar_posterior_prepare_mean(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                    int64_t n_star, const double* t_star);
 int32_t gpar_posterior_destroy(gpar_posterior* post);
 
 /* ---------------------------------------------------------------- temporal-only (LGSSM) chains
