@@ -267,6 +267,8 @@ int64_t gpar_debug_counter(const char* name) {
   if (!name) return -1;
   if (std::strcmp(name, "gains_fast") == 0) return g_gains_fast_launches.load();
   if (std::strcmp(name, "gains_general") == 0) return g_gains_general_launches.load();
+  if (std::strcmp(name, "gains_p1_lane1") == 0) return g_gains_p1_lane1_launches.load();
+  if (std::strcmp(name, "gains_p1_lane4") == 0) return g_gains_p1_lane4_launches.load();
   return -1;
 }
 

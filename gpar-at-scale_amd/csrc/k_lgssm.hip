@@ -2735,6 +2735,8 @@ namespace gpar {
 // phase-3 launches by path since the library was loaded (gpar_debug_counter "gains_fast" /
 // "gains_general"): lets a test assert which kernel a case actually ran
 std::atomic<int64_t> g_gains_fast_launches{0}, g_gains_general_launches{0};
+// phase-1 launches by lanes per chunk ("gains_p1_lane1" / "gains_p1_lane4")
+std::atomic<int64_t> g_gains_p1_lane1_launches{0}, g_gains_p1_lane4_launches{0};
 
 #define GPAR_DISPATCH_D(D, ...)                                   \
   switch (D) {                                                    \
@@ -2826,11 +2828,18 @@ void launch_gains(hipStream_t st, int sdim, const double* t, int64_t n, int L, i
   dim3 grid((unsigned)((nch + 255) / 256), (unsigned)nchains);
   GPAR_DISPATCH_D(sdim, {
     // four lanes per chunk below ~four waves per SIMD of chunks (gains_phase1)
-    if ((int64_t)nchains * nch < 4 * 1024 * 64) {
+    // (GPAR_GAINS_P1_LANES=1 / 4: that kernel at every size, for the one-lane kernel's tests --
+    // the size rule reaches it only from 262144 chunk-chains)
+    const char* pe = std::getenv("GPAR_GAINS_P1_LANES");
+    const bool force1 = pe && pe[0] == '1' && pe[1] == '\0';
+    const bool force4 = pe && pe[0] == '4' && pe[1] == '\0';
+    if (force4 || (!force1 && (int64_t)nchains * nch < 4 * 1024 * 64)) {
       dim3 g4((unsigned)((4 * nch + 255) / 256), (unsigned)nchains);
       gains_phase1<DD, 4><<<g4, 256, 0, st>>>(t, n, L, nch, cps, noise, agg);
+      g_gains_p1_lane4_launches.fetch_add(1, std::memory_order_relaxed);
     } else {
       gains_phase1<DD, 1><<<grid, 256, 0, st>>>(t, n, L, nch, cps, noise, agg);
+      g_gains_p1_lane1_launches.fetch_add(1, std::memory_order_relaxed);
     }
     gains_phase2<DD><<<nchains, 256, 0, st>>>(nch, agg, pstart);
     // the fast phase 3 stages its inputs by 16-byte LDS-DMA: every input array 16-byte aligned

@@ -115,6 +115,8 @@ inline int rec_size(int sdim) { return sdim == 3 ? 16 : (sdim == 2 ? 8 : 4); }
 // k_lgssm.hip
 // phase-3 launches of launch_gains by path (k_lgssm.hip; gpar_debug_counter)
 extern std::atomic<int64_t> g_gains_fast_launches, g_gains_general_launches;
+// phase-1 launches by lanes per chunk (GPAR_GAINS_P1_LANES forces one)
+extern std::atomic<int64_t> g_gains_p1_lane1_launches, g_gains_p1_lane4_launches;
 void launch_gains(hipStream_t st, int sdim, const double* t, int64_t n, int L, int64_t nch,
                   int nchains, const ChainParamsHost* cps_dev, const double* noise,
                   double* agg, double* pstart, double* rec, double* g, double* phi,

@@ -190,7 +190,8 @@ def _torch_runtime_first():
 
 def debug_counter(name):
     """A process-wide diagnostic counter of the library (gpar_debug_counter): "gains_fast" /
-    "gains_general" = phase-3 gains launches by kernel path."""
+    "gains_general" = phase-3 gains launches by kernel path; "gains_p1_lane1" / "gains_p1_lane4" =
+    phase-1 gains launches by lanes per chunk (GPAR_GAINS_P1_LANES=1 / 4 forces one)."""
     return int(load().gpar_debug_counter(name.encode()))
 
 

@@ -118,7 +118,9 @@ int32_t gpar_ctx_reset_stats(gpar_ctx* ctx);
 int32_t gpar_ctx_kernel_work(gpar_ctx* ctx, const char* name, double* work);
 /* Process-wide diagnostic counters (tests; no device work): "gains_fast" / "gains_general" = the
  * gains' phase-3 launches that took the LDS-DMA fast kernel / the general kernels since the library
- * was loaded.  -1 for an unknown name. */
+ * was loaded; "gains_p1_lane1" / "gains_p1_lane4" = the gains' phase-1 launches that took the
+ * one-lane-per-chunk / the four-lanes-per-chunk kernel (the size rule, or the environment variable
+ * GPAR_GAINS_P1_LANES=1 / 4, which forces one of them for tests).  -1 for an unknown name. */
 int64_t gpar_debug_counter(const char* name);
 /* Concurrency of batched calls (gpar_dtc_objective / gpar_fit with nprob > 1): lanes = 2
  * alternates the outputs' whitening + Gram between two HIP streams with separate workspaces so
