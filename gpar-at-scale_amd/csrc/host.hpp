@@ -51,7 +51,7 @@ struct gpar_ctx {
   hipEvent_t ev_dn = nullptr;                    // split round start: the dense prefix follows the context stream
   hipEvent_t ev_gr = nullptr;                    // split round: the other outputs' gains done
   hipEvent_t ev_wd = nullptr;                    // split job: its whitening is done (post_gram)
-  // gpar_posterior_prepare's two slots (PredPrep, host.hpp): ready on the side stream / free again
+  // gpar_posterior_prepare's two slots (PredPrep, host_predict.hpp): ready on the side stream / free again
   // (their prediction done on the context stream)
   hipEvent_t ev_prep_ready[2] = {nullptr, nullptr}, ev_prep_free[2] = {nullptr, nullptr};
   std::vector<gpar::PredPrep> prep;   // the two slots (sized on first use)
@@ -594,15 +594,6 @@ void eval_dtc(gpar_ctx* c, const std::vector<DevProblem>& P, const std::vector<T
                      double* out, std::vector<int>& status_out, GramOut* gram_out = nullptr,
                      const EvalAsync* async = nullptr);
 
-struct QuOut {
-  double *me, *cov, *Ucol;
-  const double *Tu, *Tl;   // L_u^-1, L_D^-1 (full lower, ld)
-  int64_t ld;
-  int nb;
-};
-
-// compute_q_u (gpar_scaled_inference.jl:141-196): Cuu without noise, D = L_u^-1 G L_u^-T + I,
-// m_e = D^-1 L_u^-1 r, cov = inv(D) = L_D^-T L_D^-1, U_u = chol(Cuu).U.
 // The Gram (beta^T beta, beta^T alpha; ld = mp) of one output at one theta, kept by the fit
 // (fit_impl) for its best evaluation so that q(u) at the fitted theta need not recompute it.
 struct GramCache {
@@ -615,64 +606,9 @@ struct FitKeep {
   std::vector<GramCache> gram;
   std::vector<char> valid;
 };
-QuOut run_q_u(gpar_ctx* c, const DevProblem& p, const Theta& th,
-                     const GramCache* gc = nullptr);
-
-// q(u) and the substitutions every prediction mode needs, for all outputs of a gpar_fit_predict
-// call at once (a batched prediction used to run them per output: the blocked Cholesky, the
-// finish, three trsm and a trsv, each a latency-bound launch of one small job, ~4 ms per output
-// and a host sync each).  Per output i: Lu, LD (chol(Cuu), chol(D)), me = m_e, w = U_u^{-1} m_e
-// = L_u^{-T} m_e, X1 = L_u^{-1}, Vm = L_D^{-1} L_u^{-1} (zero outside m x m), and for the MC / path
-// modes cov = inv(D) = X^T X, X = L_D^{-1} (the same substitutions as run_q_u + predict_impl).
-struct QuPre {
-  const double *Lu, *LD, *me, *w, *X1, *Vm, *cov;
-  int64_t ld;
-  int nb;
-};
-// The part of one output's prediction that does not read the inference inputs, queued ahead on
-// the side stream (gpar_posterior_prepare): the merged grid's gains and the adjoint's fix-up
-// vectors h for given test times.  A slot is consumed by the matching gpar_posterior_predict.
-// A slot is matched by the posterior's unique id (never by its address, which a later
-// gpar_fit_posterior may reuse after gpar_posterior_destroy), the output index and the test times.
-struct PredPrep {
-  uint64_t post_id = 0;
-  int out = -1;
-  const double* ts = nullptr;
-  int64_t n_star = 0;
-  GainsOut g{};
-  double* h = nullptr;
-  bool valid = false;
-};
-std::vector<QuPre> run_q_u_batch(gpar_ctx* c, const std::vector<DevProblem>& P,
-                                        const std::vector<Theta>& T, const FitKeep& keep,
-                                        bool want_cov);
 void chains_logpdf(gpar_ctx* c, const std::vector<const double*>& ys, int64_t n, const double* t,
                    int sdim, const double* theta, double* lml);
 
-// --------------------------------------------------------------------------- posterior paths
-// The path draws of a seed are decorrelated from its q(u) draws (gpar_path_normals exports them).
-constexpr uint64_t kPathSeedXor = 0x5851F42D4C957F2Dull;
-inline uint64_t path_seed(uint64_t seed) { return seed ^ kPathSeedXor; }
-void path_samples(gpar_ctx* c, int sdim, const GainsOut& g, const ChainParamsHost& cp,
-                         const double* t, const double* noise, int64_t n, const double* ym,
-                         const double* fx, int64_t ldfx, int S, uint64_t seed, double* F);
-void predict_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem,
-                         int64_t n_star, const double* t_star_in, const double* v_star_in,
-                         int64_t ldvs, int mode, int samples, uint64_t seed, double* mean_out,
-                         double* std_out, const GramCache* gc = nullptr, bool defer = false,
-                         const QuPre* pre = nullptr, const PredPrep* prep = nullptr);
-// The ANALYTIC mean of predict_impl without its variance: f = Cf*u w by launch_kfu_gemv and a
-// one-column smoother of y* - f on the merged grid, O((n + n*) m d) work and O(n + n*) workspace.
-// xtr (optional): the training rows' y - Kfu w (kfu_train_residual), which depends only on the
-// posterior; null: computed here.  pre / prep / defer as predict_impl's.
-void kfu_train_residual(gpar_ctx* c, const DevProblem& P, const Theta& th, const double* w,
-                        double* xtr);
-void predict_mean_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem, int64_t n_star,
-                       const double* t_star_in, const double* v_star_in, int64_t ldvs,
-                       double* mean_out, const GramCache* gc = nullptr, bool defer = false,
-                       const QuPre* pre = nullptr, const PredPrep* prep = nullptr,
-                       const double* xtr = nullptr);
-int64_t predict_mean_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d);
 void chains_smooth(gpar_ctx* c, int nchains, int64_t n, const double* t, const double* y,
                           int64_t ldy, const double* noise, int sdim,
                           const std::vector<ChainParamsHost>& cps, double* mean, double* var,
@@ -682,8 +618,6 @@ std::vector<ChainParamsHost> chain_params(const double* theta, int nchains);
 void enter(gpar_ctx* c);
 int fail(gpar_ctx* c, int code, const char* what);
 int64_t fit_ws_estimate(const gpar_ctx* c, const std::vector<DevProblem>& P);
-int64_t predict_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d, int mode,
-                                   int samples, bool fused);
 std::vector<DevProblem> attach_dist_cache(gpar_ctx* c, const std::vector<DevProblem>& P,
                                                  int64_t later_bytes);
 void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* log_theta0,
@@ -691,6 +625,8 @@ void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* lo
                      int32_t* evals_out, FitKeep* keep, int64_t later_bytes = 0);
 
 }  // namespace gpar
+
+#include "host_predict.hpp"
 
 #define API_BEGIN(ctx)                                          \
   if (!(ctx)) return GPAR_ERR_STATE;                            \

@@ -43,21 +43,6 @@ int64_t fit_ws_estimate(const gpar_ctx* c, const std::vector<DevProblem>& P) {
   return doubles * (int64_t)sizeof(double);
 }
 
-// The same for the prediction of a gpar_fit_predict call (predict_impl, merged grid of n + n_star).
-int64_t predict_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d, int mode,
-                                   int samples, bool fused) {
-  const int64_t nt = n + n_star, nch = (nt + kChunk - 1) / kChunk;
-  int64_t doubles = nt * (mp + 64)                 // whitened Cf*u + y*
-                    + n_star * ((fused ? 0 : mp) + 8 + d)   // Q rows (not with predict_var), mean / std, sorted test inputs
-                    + nt * (20 + 8 + d)            // gains records, grid, merged inputs
-                    + 4 * nch * (mp + 1) * 4       // carries
-                    + 8 * mp * mp;                 // q(u) dense
-  if (mode == GPAR_PREDICT_MC) doubles += n_star * mp + (int64_t)samples * mp + 2 * n_star * ((samples + 127) / 128);
-  if (mode == GPAR_PREDICT_PATH)   // Cf*u, fx, the data columns, their whitening and the samples
-    doubles += nt * mp + (int64_t)samples * (4 * nt + 2 * mp) + 6 * nch * samples * kSStride;
-  return doubles * (int64_t)sizeof(double);
-}
-
 // later_bytes: what the call allocates after the cache (fit_ws_estimate + predict_ws_estimate).
 std::vector<DevProblem> attach_dist_cache(gpar_ctx* c, const std::vector<DevProblem>& P,
                                                  int64_t later_bytes) {

@@ -307,13 +307,11 @@ int32_t gpar_sde_predictions(gpar_ctx* ctx, int32_t nchains, int64_t n, const do
     double* yy = ws<double>(ctx, "sp_y", (size_t)nchains * n);
     h2d(ctx, tt, t, n);
     HIPCHECK(hipMemcpy2DAsync(yy, n * sizeof(double), y, ldy * sizeof(double), n * sizeof(double), nchains, hipMemcpyHostToDevice, ctx->stream));
-    perm.resize(n_star);
-    for (int64_t i = 0; i < n_star; ++i) perm[i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return t_star[a] < t_star[b]; });
-    std::vector<double> tsh(n_star);
-    for (int64_t i = 0; i < n_star; ++i) tsh[i] = t_star[perm[i]];
+    perm = ascending_perm(t_star, n_star);
+    std::vector<double> tsh(perm.size());
+    for (size_t i = 0; i < perm.size(); ++i) tsh[i] = t_star[perm[i]];
     double* ts = ws<double>(ctx, "sp_ts", n_star);
-    h2d(ctx, ts, tsh.data(), n_star);
+    h2d(ctx, ts, perm.empty() ? t_star : tsh.data(), n_star);
     sync(ctx);
     dt = tt; dy = yy; dts = ts; ldyd = n;
   }
@@ -344,21 +342,7 @@ int32_t gpar_sde_predictions(gpar_ctx* ctx, int32_t nchains, int64_t n, const do
   launch_gather_chains(ctx->stream, mm, nt, n_star, pts, om, n_star, nchains);
   launch_gather_chains(ctx->stream, vv, nt, n_star, pts, ov, n_star, nchains);
   check_launch("sde_predictions");
-  if (mem == GPAR_MEM_DEVICE) {
-    HIPCHECK(hipMemcpyAsync(mean, om, (size_t)nchains * n_star * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHECK(hipMemcpyAsync(var, ov, (size_t)nchains * n_star * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    sync(ctx);
-  } else {
-    std::vector<double> hm((size_t)nchains * n_star), hv((size_t)nchains * n_star);
-    d2h(ctx, hm.data(), om, hm.size());
-    d2h(ctx, hv.data(), ov, hv.size());
-    sync(ctx);
-    for (int b = 0; b < nchains; ++b)
-      for (int64_t i = 0; i < n_star; ++i) {
-        mean[(size_t)b * n_star + perm[i]] = hm[(size_t)b * n_star + i];
-        var[(size_t)b * n_star + perm[i]] = hv[(size_t)b * n_star + i];
-      }
-  }
+  deliver(ctx, mem, perm, /*defer=*/false, n_star, {{om, mean}, {ov, var}}, nchains);
   API_END(ctx)
 }
 
