@@ -366,8 +366,11 @@ int32_t gpar_pairwise_distances(gpar_ctx* ctx, const gpar_problem* prob, double*
   DevProblem p = prepare_problem(ctx, *prob, 0);
   // the fit's distance-cache kernel, as gpar_fit fills a cache slot (attach_dist_cache)
   double* d = ws<double>(ctx, "pw_dist", (size_t)p.n * p.mp);
-  launch_dist2(ctx->stream, p.ok, p.v, p.ldv, p.n, p.z, p.ldz, p.m, p.mp, (int)p.d, p.zc, d, p.mp,
-               /*take_sqrt=*/p.ok != GPAR_EQ);
+  {
+    Timed td_(ctx, "dist2", 2.0 * (double)p.n * (double)p.mp * (double)p.d);
+    launch_dist2(ctx->stream, p.ok, p.v, p.ldv, p.n, p.z, p.ldz, p.m, p.mp, (int)p.d, p.zc, d,
+                 p.mp, /*take_sqrt=*/p.ok != GPAR_EQ);
+  }
   check_launch("dist2 (pairwise)");
   HIPCHECK(hipMemcpy2DAsync(dist_out, p.m * sizeof(double), d, p.mp * sizeof(double),
                             p.m * sizeof(double), p.n,

@@ -304,6 +304,36 @@ void launch_mean_finish(hipStream_t st, int sdim, const double* u, const double*
                         const double* fstar, const int64_t* pos, int64_t nstar, int L,
                         double* mean);
 
+// k_kmeans.hip (pseudo-input selection: Lloyd's k-means, layouts in the file header)
+// g[i] = mean over the m centres of z[c][i], i < d (the centre the assignment's Gram form is
+// taken about)
+void launch_kmeans_center(hipStream_t st, const double* z, int64_t ldz, int64_t m, int d,
+                          double* g);
+int64_t kmeans_assign_blocks(int64_t n);
+// label[k] = the nearest centre of v_k (lowest index among equal computed distances), dmin[k] its
+// squared distance (clamped at 0), count[c] += members (zeroed by the caller), ipart[b] = the sum
+// of dmin over row tile b (kmeans_assign_blocks(n) doubles)
+void launch_kmeans_assign(hipStream_t st, const double* v, int64_t ldv, int64_t n, const double* z,
+                          int64_t ldz, int64_t m, int d, const double* g, int32_t* label,
+                          double* dmin, unsigned long long* count, double* ipart);
+// *out = sum of the nb partials, in fixed order
+void launch_kmeans_inertia(hipStream_t st, const double* ipart, int64_t nb, double* out);
+// row splits of the update's partial sums (a function of the sizes alone), part: splits x m x d
+// pairs of doubles (sum, compensation)
+int kmeans_sum_splits(int64_t n, int64_t m, int d);
+// z[c] = mean of the rows labelled c (part summed over the splits in order) where count[c] > 0;
+// other centres untouched
+void launch_kmeans_update(hipStream_t st, const double* v, int64_t ldv, int64_t n,
+                          const int32_t* label, const unsigned long long* count, int64_t m, int d,
+                          double* part, double* z, int64_t ldz);
+// snap: best[c] = min over members of dmin's bit pattern, then idx[c] = the lowest member row
+// attaining it, then z[c] = v[idx[c]]; best and idx start as all ones, which idx keeps for an
+// empty cluster (-1 as int64)
+void launch_kmeans_snap(hipStream_t st, const double* v, int64_t ldv, int64_t n,
+                        const int32_t* label, const double* dmin, int64_t m, int d,
+                        unsigned long long* best, unsigned long long* idx, double* z,
+                        int64_t ldz);
+
 // k_path.hip (posterior path sampling: the simulation smoother batched over samples; layouts in
 // the file header)
 void launch_kfu_from_dist(hipStream_t st, int out_kind, double* K, int64_t n, int64_t m,

@@ -30,6 +30,7 @@ EXPORTED = (
     "gpar_fit_posterior", "gpar_posterior_predict", "gpar_posterior_prepare", "gpar_posterior_destroy",
     "gpar_predict_mean", "gpar_posterior_predict_mean", "gpar_posterior_prepare_mean",
     "gpar_nm_create", "gpar_nm_destroy", "gpar_nm_ask", "gpar_nm_tell", "gpar_nm_result",
+    "gpar_select_pseudo_inputs",
 )
 
 
@@ -109,6 +110,8 @@ def load(path: str | None = None):
             "gpar_ctx_set_dist_cache_keep": (i32, [vp, i32]),
             "gpar_ctx_dist_cache_stats": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]),
             "gpar_pairwise_distances": (i32, [vp, C.POINTER(GparProblem), dp]),
+            "gpar_select_pseudo_inputs": (i32, [vp, i64, i64, dp, i64, i64, dp, i64, i32, i32, i32,
+                                                dp, i64, vp, vp, vp, dp]),
             "gpar_ctx_set_input_stream": (i32, [vp, vp, i32]),
             "gpar_dtc_objective": (i32, [vp, C.POINTER(GparProblem), i32, dp, dp]),
             "gpar_dtc_objective_A": (i32, [vp, C.POINTER(GparProblem), dp, dp, dp]),

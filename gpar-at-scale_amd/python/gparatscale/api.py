@@ -256,6 +256,81 @@ def pairwise_distances(V, Z, out_kernel="matern52", device=0):
     return out
 
 
+# ----------------------------------------------------------------------------- pseudo-input selection
+@dataclass
+class PseudoInputs:
+    """select_pseudo_inputs' result.  Z: the centres, laid out as the inputs were (host: D x M
+    ColVecs, device: M x D tensor), ready to pass on as pseudo_input_locations; index: [M] the row
+    of V each centre was snapped to (-1: empty cluster, or snap=False); labels: [N] each input's
+    centre; counts: [M] members per centre; inertia: [iters + 1] host array, the sum of squared
+    distances of every assignment pass (labels / counts / inertia[-1] refer to the centres before
+    the snap)."""
+    Z: object
+    index: object
+    labels: object
+    counts: object
+    inertia: np.ndarray
+
+
+def select_pseudo_inputs(V, Z0_or_M, iters=10, snap=True, seed=0, device=0):
+    """Place M pseudo-inputs over the inputs V by Lloyd's k-means on the GPU
+    (gpar_select_pseudo_inputs): `iters` rounds from the start centres, then with snap=True every
+    non-empty cluster's centre is replaced by its member row nearest to it, so Z is M distinct rows
+    of V.  V: host D x N (ColVecs) or a device tensor N x D (rows = points; a column-prefix view of
+    a wider matrix is read in place).  Z0_or_M: the start centres, laid out like V, or an integer
+    M: the rows data.pseudo_index(N, M, seed) of V.  Deterministic."""
+    from . import data
+    ctx, lib = context(device), _lib.load()
+    keep = _Keep()
+    dev = _is_torch(V)
+    if dev:
+        import torch
+        vp, ldv, n, d = _dev_points(V, keep)
+        Vr = keep[-1]
+        if isinstance(Z0_or_M, (int, np.integer)):
+            if not 1 <= int(Z0_or_M) <= n:
+                raise _arg_error("M must be in 1..N")
+            rows = torch.as_tensor(data.pseudo_index(n, int(Z0_or_M), seed), device=Vr.device)
+            Z0 = Vr[rows]
+        else:
+            Z0 = Z0_or_M
+        zp, ldz, m, dz = _dev_points(Z0, keep)
+        if dz != d:
+            raise _arg_error("V and Z0 must have the same dimension")
+        opt = dict(device=Vr.device)
+        Z = torch.empty((m, d), dtype=torch.float64, **opt)
+        index = torch.empty(m, dtype=torch.int64, **opt)
+        labels = torch.empty(n, dtype=torch.int32, **opt)
+        counts = torch.empty(m, dtype=torch.int64, **opt)
+        ptr = lambda a: C.c_void_p(a.data_ptr())
+        mem = _lib.GPAR_MEM_DEVICE
+    else:
+        vp, ldv, n, d = _host_points(V, keep)
+        Vr = keep[-1]
+        if isinstance(Z0_or_M, (int, np.integer)):
+            if not 1 <= int(Z0_or_M) <= n:
+                raise _arg_error("M must be in 1..N")
+            Z0 = Vr[data.pseudo_index(n, int(Z0_or_M), seed)].T
+        else:
+            Z0 = Z0_or_M
+        zp, ldz, m, dz = _host_points(Z0, keep)
+        if dz != d:
+            raise _arg_error("V and Z0 must have the same dimension")
+        Z = np.zeros((m, d))
+        index = np.zeros(m, dtype=np.int64)
+        labels = np.zeros(n, dtype=np.int32)
+        counts = np.zeros(m, dtype=np.int64)
+        ptr = _ptr
+        mem = _lib.GPAR_MEM_HOST
+    inertia = np.zeros(max(int(iters), 0) + 1)
+    with _after_torch(ctx, dev):
+        ctx.check(lib.gpar_select_pseudo_inputs(
+            ctx.h, n, d, C.c_void_p(vp), ldv, m, C.c_void_p(zp), ldz, int(iters),
+            1 if snap else 0, mem, ptr(Z), d, ptr(index), ptr(labels), ptr(counts),
+            _ptr(inertia)))
+    return PseudoInputs(Z if dev else np.ascontiguousarray(Z.T), index, labels, counts, inertia)
+
+
 # ----------------------------------------------------------------------------- fit
 @dataclass
 class FitResult:

@@ -276,6 +276,27 @@ int32_t gpar_dtc_objective_A(gpar_ctx* ctx, const gpar_problem* prob, const doub
  * distance for EQ.  n x m, in prob->mem.  For parity checks of the cache. */
 int32_t gpar_pairwise_distances(gpar_ctx* ctx, const gpar_problem* prob, double* dist_out);
 
+/* Pseudo-input selection: Lloyd's k-means over the n inputs v (point k dim i at v[k*ldv + i]),
+ * started from the m centres z0.  iters >= 0 rounds of {assign every point to its nearest centre
+ * (lowest index on ties); move every non-empty cluster's centre to its members' mean}, then one
+ * more assignment against the final centres, which label_out / count_out / the last inertia refer to.
+ * snap = 1: each non-empty cluster's centre is then replaced by its member row nearest to it
+ * (lowest row on ties), index_out[c] = that row; index_out[c] = -1 for an empty cluster or snap = 0.
+ * v, z0, z_out (m x d, ld ldz_out), index_out [m], label_out [n], count_out [m] in `mem`;
+ * inertia_out [iters + 1] host (the sum of squared distances of each assignment pass).
+ * Any of index_out, label_out, count_out, inertia_out may be NULL.  Deterministic: the same inputs
+ * give the same bits, in either memory space.  z_out may alias z0.  An empty cluster keeps its
+ * centre bit for bit.  Distances are the centred Gram form |v - g|^2 + |z - g|^2 - 2 (v - g).(z - g)
+ * about the mean g of the current centres, clamped at 0 (fp64 MFMA, any d).  GPAR_ERR_ARG for
+ * n < 1, d < 1, m < 1, m > n, a stride below d, iters < 0, a NULL v, z0 or z_out, or an unknown
+ * mem.  Event-timing family "kmeans" (gpar_ctx_kernel_stats; gpar_ctx_kernel_work: flops,
+ * 2 n m d per assignment pass). */
+int32_t gpar_select_pseudo_inputs(gpar_ctx* ctx, int64_t n, int64_t d, const double* v, int64_t ldv,
+                                  int64_t m, const double* z0, int64_t ldz0, int32_t iters,
+                                  int32_t snap, int32_t mem, double* z_out, int64_t ldz_out,
+                                  int64_t* index_out, int32_t* label_out, int64_t* count_out,
+                                  double* inertia_out);
+
 /* ---------------------------------------------------------------- fit
  * Replaces get_optim_scaled_gpar_params (src/gp/dtc.jl:11-77): Nelder-Mead over the 5
  * log-hyperparameters maximising the DTC objective, batched over nprob outputs (one GPU

@@ -15,6 +15,10 @@ and adds the multi-output driver the reference writes as a loop in its examples
 
   get_gpar_scaled_predictions_batch  -> (means, stds), one vector per output, one library call
 
+and the chooser of pseudo-inputs the reference leaves to its caller (k-means on the GPU):
+
+  select_pseudo_inputs               -> (Z, index, labels, counts, inertia)
+
 with every number computed by the gfx950 kernels behind include/gpar_hip.h.  A caller switches
 `using GPARatScale` to `using GPARatScale, GPARatScaleHIP` and qualifies these five names (or
 imports them from GPARatScaleHIP).  The reference's helpers (to_ColVecs, unpack_gpar,
@@ -38,7 +42,8 @@ using GPARatScale: to_ColVecs, unpack_gpar, unpack_gp, parse_initial_gpar_params
                    parse_initial_gp_params
 
 export compute_gpar_dtc_objective, get_optim_scaled_gpar_params, compute_q_u,
-       get_gpar_scaled_predictions, get_sde_predictions, get_gpar_scaled_predictions_batch
+       get_gpar_scaled_predictions, get_sde_predictions, get_gpar_scaled_predictions_batch,
+       select_pseudo_inputs
 
 const libgpar = get(ENV, "GPAR_HIP_LIB", "libgparhip.so")
 
@@ -508,6 +513,41 @@ function get_gpar_scaled_predictions_batch(Y::AbstractMatrix, pseudo_input_locat
         end
     end
     return means, stds
+end
+
+# ------------------------------------------------------------------ pseudo-input selection
+"""
+    select_pseudo_inputs(input_locations, pseudo_input_locations; iters = 10, snap = true)
+
+Places the pseudo-inputs over `input_locations` by Lloyd's k-means on the GPU, started from
+`pseudo_input_locations` (e.g. a random subset of the inputs, as the reference's examples pass):
+`iters` rounds, then with `snap = true` every non-empty cluster's centre is replaced by its member
+input nearest to it.  Returns (Z, index, labels, counts, inertia): Z a D x M matrix to pass on as
+pseudo_input_locations, index the 1-based input each centre was snapped to (0: empty cluster or
+`snap = false`), labels the 1-based centre of every input, counts the members per centre, inertia
+the sum of squared distances of each of the `iters + 1` assignment passes.
+"""
+function select_pseudo_inputs(input_locations, pseudo_input_locations; iters::Integer = 10,
+                              snap::Bool = true)
+    V = _colmat(input_locations)
+    Z0 = _colmat(pseudo_input_locations)
+    size(V, 1) == size(Z0, 1) || throw(DomainError(size(Z0, 1), "V and Z dimensions differ"))
+    D, N, M = size(V, 1), size(V, 2), size(Z0, 2)
+    Z = zeros(D, M)
+    index = zeros(Int64, M)
+    labels = zeros(Int32, N)
+    counts = zeros(Int64, M)
+    inertia = zeros(max(iters, 0) + 1)
+    c = ctx()
+    GC.@preserve V Z0 Z index labels counts inertia begin
+        check(c, ccall((:gpar_select_pseudo_inputs, libgpar), Int32,
+                       (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                        Int32, Int32, Int32, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int32},
+                        Ptr{Int64}, Ptr{Float64}),
+                       c.h, N, D, V, D, M, Z0, D, Int32(iters), Int32(snap), GPAR_MEM_HOST, Z, D,
+                       index, labels, counts, inertia))
+    end
+    return Z, index .+ 1, labels .+ Int32(1), counts, inertia
 end
 
 # ------------------------------------------------------------------ temporal_gp_inference.jl:45-114
