@@ -274,6 +274,23 @@ int32_t gpar_posterior_predict(gpar_ctx* ctx, const gpar_posterior* post, int32_
   API_END(ctx)
 }
 
+int32_t gpar_posterior_predict_samples(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                       int64_t n_star, const double* t_star,
+                                       const double* v_shared, int64_t ldvs, int64_t d_shared,
+                                       const double* v_samp, int64_t ld_s, int64_t ld_r,
+                                       int32_t samples, uint64_t seed, double* f_out,
+                                       int64_t ldf_s, int64_t ldf_r, double* mean, double* std) {
+  API_BEGIN(ctx)
+  ARGCHECK(post, "null argument");
+  const gpar_posterior::Out& o = posterior_output(ctx, post, i, n_star);
+  check_sample_args(o.p.d, n_star, t_star, v_shared, ldvs, d_shared, v_samp, ld_s, ld_r, samples,
+                    f_out, ldf_s, ldf_r);
+  const PredPrep* prep = take_prep(ctx, post, i, n_star, t_star);
+  predict_samples_impl(ctx, o.p, o.th, post->mem, n_star, t_star, v_shared, ldvs, d_shared, v_samp,
+                       ld_s, ld_r, samples, seed, f_out, ldf_s, ldf_r, mean, std, &o.q, prep);
+  API_END(ctx)
+}
+
 int32_t gpar_posterior_destroy(gpar_posterior* post) {
   delete post;
   return GPAR_OK;

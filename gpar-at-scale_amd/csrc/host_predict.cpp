@@ -1,6 +1,6 @@
 // host_predict.cpp -- the prediction stages (test inputs, merged grid, gains, the Sigma^{-1} solve,
-// delivery), the prediction modes built from them (analytic, MC, posterior paths, mean only), their
-// workspace estimates and the single-output C-ABI entries.
+// delivery), the prediction modes built from them (analytic, MC, posterior paths, paths with
+// per-sample test inputs, mean only), their workspace estimates and the single-output C-ABI entries.
 #include "host.hpp"
 
 namespace gpar {
@@ -58,7 +58,7 @@ static TestInputs stage_test_inputs(gpar_ctx* c, int mem, int64_t n_star, int64_
   perm = ascending_perm(t_star_in, n_star);
   if (perm.empty()) {
     h2d(c, dts, t_star_in, n_star);
-    h2d_rows(c, dvs, v_star_in, ldvs, d, n_star);
+    if (d > 0) h2d_rows(c, dvs, v_star_in, ldvs, d, n_star);   // (0: no column every sample shares)
   } else {
     std::vector<double> tsh(n_star), vsh((size_t)n_star * d);
     for (int64_t i = 0; i < n_star; ++i) {
@@ -77,7 +77,8 @@ static TestInputs stage_test_inputs(gpar_ctx* c, int mem, int64_t n_star, int64_
 
 MergedGrid merge_grid(gpar_ctx* c, const std::string& tag, const DevProblem& P, double s2,
                       const double* ts, int64_t n_star, const double* ycol, const double* vs,
-                      int64_t ldvs, bool want_inputs, bool want_pos, const char* yname) {
+                      int64_t ldvs, bool want_inputs, bool want_pos, const char* yname,
+                      bool want_tpos) {
   MergedGrid g{};
   const int64_t n = P.n, d = want_inputs ? P.d : 0;
   g.nt = n + n_star;
@@ -87,8 +88,9 @@ MergedGrid merge_grid(gpar_ctx* c, const std::string& tag, const DevProblem& P, 
   g.rm = ws<double>(c, tag + "_rm", g.nt);
   if (want_inputs) g.vm = ws<double>(c, tag + "_vm", (size_t)g.nt * d);
   if (want_pos) g.pos = ws<int64_t>(c, tag + "_pos", n_star);
+  if (want_tpos) g.tpos = ws<int64_t>(c, tag + "_tpos", n);
   launch_merge_side(c->stream, P.t, n, ts, n_star, 0, ycol, s2, want_inputs ? P.v : nullptr,
-                    want_inputs ? P.ldv : 0, (int)d, g.tm, g.ym, g.rm, g.vm, d, nullptr);
+                    want_inputs ? P.ldv : 0, (int)d, g.tm, g.ym, g.rm, g.vm, d, g.tpos);
   launch_merge_side(c->stream, ts, n_star, P.t, n, 1, nullptr, 1e10, want_inputs ? vs : nullptr,
                     want_inputs ? ldvs : 0, (int)d, g.tm, g.ym, g.rm, g.vm, d, g.pos);
   return g;
@@ -244,27 +246,67 @@ struct Pred {
   // PATH (tmp.jl:119-167): per sample, fx_s = Cf*u U_u^{-1} e_s (e_s ~ q(u)) on the merged grid, then a
   // posterior path of the time GP given y* - fx_s (simulation smoother, path_samples), f*_s = fx_s + f_t,s
   MeanStd path_tail() const {
-    const int64_t m = P.m, d = P.d, mp = P.mp, nt = grid.nt;
     const McFactor f = mc_factor();
+    const double* Bm = sample_loadings(f);
+    double* FX = ws<double>(c, "pr_FX", (size_t)grid.nt * samples);
+    shared_input_fx(grid.vm, P.d, grid.nt, Bm, FX);
+    check_launch("predict: path fx");
+    path_draws(FX);
+    f.check(c);
+    return {mean, std};
+  }
+
+  // the pseudo-point samples' loadings Bm (samples x mp): U_u^{-1} (m_e + Lc xi_s), xi = gpar_mc_normals
+  const double* sample_loadings(const McFactor& f) const {
+    const int64_t m = P.m, mp = P.mp;
     double* xi = ws<double>(c, "pr_xi", (size_t)samples * mp);
     launch_normal(c->stream, xi, mp, samples, m, samples, seed);
     double* Bm = ws<double>(c, "pr_Bm", (size_t)samples * mp);
     launch_path_bmat(c->stream, f.W, q.ld, q.w, xi, mp, samples, (int)m, mp, Bm, mp);
-    double* Ks = ws<double>(c, "pr_Ks", (size_t)nt * mp);   // Cf*u (gpar_scaled_inference.jl:89)
-    launch_dist2(c->stream, P.ok, grid.vm, d, nt, P.z, P.ldz, m, mp, (int)d, P.zc, Ks, mp,
+    return Bm;
+  }
+
+  // fx (rows x samples, packed) = Cf*u Bm^T at `rows` inputs every sample shares: Cf*u stored
+  void shared_input_fx(const double* v, int64_t ldv, int64_t rows, const double* Bm,
+                       double* fx) const {
+    const int64_t m = P.m, d = P.d, mp = P.mp;
+    double* Ks = ws<double>(c, "pr_Ks", (size_t)rows * mp);   // Cf*u (gpar_scaled_inference.jl:89)
+    launch_dist2(c->stream, P.ok, v, ldv, rows, P.z, P.ldz, m, mp, (int)d, P.zc, Ks, mp,
                  /*take_sqrt=*/P.ok != GPAR_EQ);
-    launch_kfu_from_dist(c->stream, P.ok, Ks, nt, m, mp, 1.0 / th.l_o, th.sv_o * th.sv_o);
-    double* FX = ws<double>(c, "pr_FX", (size_t)nt * samples);
-    // FX only: no row sums (mode 0 writes them per 128-column block when asked)
-    launch_gemm_nt(c->stream, Ks, mp, Bm, mp, nt, samples, m, 0, FX, samples, nullptr, 0, nullptr,
+    launch_kfu_from_dist(c->stream, P.ok, Ks, rows, m, mp, 1.0 / th.l_o, th.sv_o * th.sv_o);
+    // fx only: no row sums (mode 0 writes them per 128-column block when asked)
+    launch_gemm_nt(c->stream, Ks, mp, Bm, mp, rows, samples, m, 0, fx, samples, nullptr, 0, nullptr,
                    nullptr, nullptr, 0);
-    check_launch("predict: path fx");
-    double* F = ws<double>(c, "pr_F", (size_t)nt * samples);
-    path_samples(c, P.sdim, gg.g, cp, grid.tm, grid.rm, nt, grid.ym, FX, samples, samples, seed, F);
+  }
+
+  // the posterior paths given y* - FX and their statistics at the test rows; returns F
+  const double* path_draws(const double* FX) const {
+    double* F = ws<double>(c, "pr_F", (size_t)grid.nt * samples);
+    path_samples(c, P.sdim, gg.g, cp, grid.tm, grid.rm, grid.nt, grid.ym, FX, samples, samples, seed,
+                 F);
     launch_path_stats(c->stream, FX, samples, F, samples, grid.pos, n_star, mean, std);
     check_launch("predict: path stats");
-    f.check(c);
-    return {mean, std};
+    return F;
+  }
+
+  // SAMPLES: FX when every sample has its own test inputs.  The training rows use the shared
+  // training inputs (shared_input_fx over the n training rows alone, scattered to their merged
+  // rows); the test rows come from launch_kfu_samples, which stores no kernel matrix.
+  double* per_sample_fx(const TestInputs& ti, int64_t d_sh, const double* vsa, int64_t ld_s,
+                        int64_t ld_r, const int64_t* dperm, const double* Bm) const {
+    const int64_t d_sa = P.d - d_sh;
+    double* FX = ws<double>(c, "pr_FX", (size_t)grid.nt * samples);
+    double* fxtr = ws<double>(c, "ps_fxtr", (size_t)P.n * samples);
+    shared_input_fx(P.v, P.ldv, P.n, Bm, fxtr);
+    launch_scatter_rows(c->stream, fxtr, P.n, samples, grid.tpos, FX, samples);
+    {   // flops of the distance contractions; the samples * n* * m kernel evaluations come on top
+      Timed tm_(c, "pred_sfx", 2.0 * (double)samples * (double)n_star * (double)P.m * (double)P.d);
+      launch_kfu_samples(c->stream, P.ok, ti.vs, ti.ldv, (int)d_sh, vsa, ld_s, ld_r, (int)d_sa, dperm,
+                         n_star, samples, P.z, P.ldz, P.m, P.zc, Bm, P.mp, 1.0 / th.l_o,
+                         th.sv_o * th.sv_o, grid.pos, FX, samples);
+    }
+    check_launch("predict samples: fx");
+    return FX;
   }
 
   // ANALYTIC / MC, first half: the Cf*u columns (on the fly) and y* whitened into X, and
@@ -407,6 +449,91 @@ int64_t predict_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d, in
   return doubles * (int64_t)sizeof(double);
 }
 
+// --------------------------------------------------------------------------- sample-chained prediction
+// Path mode with per-sample test inputs, its samples delivered (host_predict.hpp): predict_impl's
+// stages with per_sample_fx in place of the shared-input Cf*u product.
+void predict_samples_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem,
+                          int64_t n_star, const double* t_star_in, const double* v_sh_in,
+                          int64_t ldvs, int64_t d_sh, const double* v_sa_in, int64_t ld_s,
+                          int64_t ld_r, int samples, uint64_t seed, double* f_out, int64_t ldf_s,
+                          int64_t ldf_r, double* mean_out, double* std_out, const QuPre* pre,
+                          const PredPrep* prep) {
+  // path draw (s, k, i): counter index k (sdim + 1) + i, 32 bits
+  ARGCHECK((P.n + n_star) * (P.sdim + 1) <= ((int64_t)1 << 32),
+           "sample prediction: (n + n_star) * (state dimension + 1) must be <= 2^32");
+  const int64_t d_sa = P.d - d_sh;
+  const TestInputs ti = stage_test_inputs(c, mem, n_star, d_sh, t_star_in, v_sh_in, ldvs);
+  // the sample inputs: device tensors are read in place; host ones are uploaded packed, in the
+  // caller's row order -- the kernel gathers rows through the sort permutation either way
+  const double* vsa = v_sa_in;
+  const int64_t* dperm = nullptr;
+  if (mem == GPAR_MEM_HOST && d_sa > 0) {
+    double* dv = ws<double>(c, "ps_vsa", (size_t)samples * n_star * d_sa);
+    if (ld_r == d_sa && ld_s == n_star * d_sa)
+      h2d(c, dv, v_sa_in, (size_t)samples * n_star * d_sa);
+    else
+      for (int s = 0; s < samples; ++s)
+        h2d_rows(c, dv + (size_t)s * n_star * d_sa, v_sa_in + (size_t)s * ld_s, ld_r, d_sa, n_star);
+    vsa = dv;
+    ld_r = d_sa;
+    ld_s = n_star * d_sa;
+    if (!ti.perm.empty()) {
+      int64_t* dp = ws<int64_t>(c, "ps_perm", n_star);
+      h2d(c, dp, ti.perm.data(), n_star);
+      dperm = dp;
+    }
+  }
+  Pred s{c, P, th, n_star, samples, seed};
+  s.q = qu_factors(c, P, th, nullptr, pre, /*want_cov=*/true);
+  check_launch("predict samples: q(u) tail");
+  const double s2 = th.sigma * th.sigma;
+  s.grid = merge_grid(c, "pr", P, s2, ti.ts, n_star, P.y, nullptr, 0, /*want_inputs=*/false,
+                      /*want_pos=*/true, "_ym", /*want_tpos=*/true);
+  check_launch("predict samples: merge");
+  s.cp = chain_params_of(th, s2);   // noise sigma^2 train / 1e10 test
+  s.gg = grid_gains(c, P.sdim, s.cp, s.grid, prep, "pred");
+  s.mean = ws<double>(c, "pr_mean", n_star);
+  s.std = ws<double>(c, "pr_std", n_star);
+  const McFactor f = s.mc_factor();
+  const double* Bm = s.sample_loadings(f);
+  const double* FX = s.per_sample_fx(ti, d_sh, vsa, ld_s, ld_r, dperm, Bm);
+  const double* F = s.path_draws(FX);
+  release_prep(c, prep);
+  // ---- delivery: the samples (strided destination, caller's row order), then mean and std
+  if (mem == GPAR_MEM_DEVICE) {
+    launch_sample_values(c->stream, FX, samples, F, samples, s.grid.pos, n_star, f_out, ldf_s, ldf_r);
+    check_launch("predict samples: values");
+  } else {
+    double* dout = ws<double>(c, "ps_out", (size_t)samples * n_star);
+    launch_sample_values(c->stream, FX, samples, F, samples, s.grid.pos, n_star, dout, n_star, 1);
+    check_launch("predict samples: values");
+    std::vector<double> h((size_t)samples * n_star);
+    d2h(c, h.data(), dout, h.size());
+    sync(c);   // every input is uploaded and read: f_out may now overwrite a column of v_sa's tensor
+    for (int b = 0; b < samples; ++b)
+      for (int64_t i = 0; i < n_star; ++i)
+        f_out[b * ldf_s + (ti.perm.empty() ? i : ti.perm[i]) * ldf_r] = h[(size_t)b * n_star + i];
+  }
+  f.check(c);
+  if (mean_out) deliver(c, mem, ti.perm, false, n_star, {{s.mean, mean_out}});
+  if (std_out) deliver(c, mem, ti.perm, false, n_star, {{s.std, std_out}});
+  if (!mean_out && !std_out && mem == GPAR_MEM_DEVICE) sync(c);
+}
+
+// Device bytes of predict_samples_impl's workspace: path mode's without the merged inputs and with
+// Cf*u over the training rows only, plus the training rows' fx and the positions.
+int64_t predict_samples_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d_sh,
+                                    int64_t d_sa, int samples, bool host) {
+  const int64_t nt = n + n_star, nch = (nt + kChunk - 1) / kChunk;
+  int64_t doubles = nt * (20 + 8)                       // gains records, fix-up rows, grid
+                    + n + n_star * (4 + d_sh)           // positions, mean / std, sorted shared inputs
+                    + 8 * mp * mp                       // q(u) dense, Lc, W
+                    + n * mp + (int64_t)samples * (n + 4 * nt + 2 * mp)   // Cf*u (train), fx, z, X, F, xi, Bm
+                    + 6 * nch * samples * kSStride + 4 * nch * 4;         // carries
+  if (host) doubles += (int64_t)samples * n_star * (d_sa + 1) + n_star;   // staged inputs, outputs, perm
+  return doubles * (int64_t)sizeof(double);
+}
+
 // --------------------------------------------------------------------------- mean-only prediction
 // The ANALYTIC mean alone (gpar_scaled_inference.jl:91-97 with e = m_e): with w = U_u^{-1} m_e,
 //   f = Cf*u w on the merged grid,  mean_i = f_k + (S (y* - f))_k,  k = pos[i],
@@ -499,6 +626,21 @@ int32_t gpar_predict_mean(gpar_ctx* ctx, const gpar_problem* prob, const double*
   ARGCHECK(ldvs >= prob->d, "ldvs must be >= d");
   const DevProblem P = prepare_problem(ctx, *prob, 0);
   predict_mean_impl(ctx, P, thetas_from(theta, 1)[0], prob->mem, n_star, t_star, v_star, ldvs, mean);
+  API_END(ctx)
+}
+
+int32_t gpar_predict_samples(gpar_ctx* ctx, const gpar_problem* prob, const double* theta,
+                             int64_t n_star, const double* t_star, const double* v_shared,
+                             int64_t ldvs, int64_t d_shared, const double* v_samp, int64_t ld_s,
+                             int64_t ld_r, int32_t samples, uint64_t seed, double* f_out,
+                             int64_t ldf_s, int64_t ldf_r, double* mean, double* std) {
+  API_BEGIN(ctx)
+  ARGCHECK(prob && theta, "null argument");
+  check_sample_args(prob->d, n_star, t_star, v_shared, ldvs, d_shared, v_samp, ld_s, ld_r, samples,
+                    f_out, ldf_s, ldf_r);
+  const DevProblem P = prepare_problem(ctx, *prob, 0);
+  predict_samples_impl(ctx, P, thetas_from(theta, 1)[0], prob->mem, n_star, t_star, v_shared, ldvs,
+                       d_shared, v_samp, ld_s, ld_r, samples, seed, f_out, ldf_s, ldf_r, mean, std);
   API_END(ctx)
 }
 

@@ -51,15 +51,18 @@ void deliver(gpar_ctx* c, int mem, const std::vector<int64_t>& perm, bool defer,
 
 // Train and test points merged in time order: times tm, the data column ym (ycol on the train
 // rows, 0 on the test rows), noise rm (s2 train / 1e10 test), with want_inputs the inputs vm
-// (ld d), with want_pos the test points' merged rows pos.  Workspace names tag + "_tm", ...
+// (ld d), with want_pos the test points' merged rows pos, with want_tpos the training points'
+// tpos.  Workspace names tag + "_tm", ...
 struct MergedGrid {
   double *tm, *ym, *rm, *vm;
   int64_t* pos;
   int64_t nt, nch;
+  int64_t* tpos;
 };
 MergedGrid merge_grid(gpar_ctx* c, const std::string& tag, const DevProblem& P, double s2,
                       const double* ts, int64_t n_star, const double* ycol, const double* vs,
-                      int64_t ldvs, bool want_inputs, bool want_pos, const char* yname = "_ym");
+                      int64_t ldvs, bool want_inputs, bool want_pos, const char* yname = "_ym",
+                      bool want_tpos = false);
 
 // The merged grid's gains, and the adjoint's fix-up rows h once something has computed them
 // (fixup_rows).  gpar_posterior_prepare fills one ahead of the prediction (PredPrep).
@@ -142,9 +145,45 @@ void predict_mean_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int me
                        double* mean_out, const GramCache* gc = nullptr, bool defer = false,
                        const QuPre* pre = nullptr, const PredPrep* prep = nullptr,
                        const double* xtr = nullptr);
+// Sample-chained prediction: path mode (GPAR_PREDICT_PATH) with per-sample test inputs and the
+// samples delivered.  Test row i of sample s sits at [v_sh_i (d_sh columns, ld ldvs) , v_sa_{s,i}
+// (d_sa = P.d - d_sh columns at v_sa[s * ld_s + i * ld_r + .])]; the draws are path mode's for
+// (samples, seed), so with d_sa = 0 this is predict_impl's path mode with its samples exposed.
+// f_out[s * ldf_s + i * ldf_r] = sample s at test point i (the caller's row order); mean_out /
+// std_out (either may be null): the sample mean and Bessel std, as path mode reduces them
+// (samples = 1: the std is 0 / 0).  f_out may lie in the tensor v_sa points into, at a column this
+// call does not read: everything is read before anything is delivered.  pre / prep as predict_impl's.
+void predict_samples_impl(gpar_ctx* c, const DevProblem& P, const Theta& th, int mem,
+                          int64_t n_star, const double* t_star_in, const double* v_sh_in,
+                          int64_t ldvs, int64_t d_sh, const double* v_sa_in, int64_t ld_s,
+                          int64_t ld_r, int samples, uint64_t seed, double* f_out, int64_t ldf_s,
+                          int64_t ldf_r, double* mean_out, double* std_out,
+                          const QuPre* pre = nullptr, const PredPrep* prep = nullptr);
+// The argument checks gpar_predict_samples and gpar_posterior_predict_samples share (d: the
+// problem's input dimension).
+inline void check_sample_args(int64_t d, int64_t n_star, const double* t_star, const double* v_sh,
+                              int64_t ldvs, int64_t d_sh, const double* v_sa, int64_t ld_s,
+                              int64_t ld_r, int samples, const double* f_out, int64_t ldf_s,
+                              int64_t ldf_r) {
+  ARGCHECK(t_star && f_out, "null argument");
+  ARGCHECK(n_star >= 1, "n_star must be >= 1");
+  ARGCHECK(d_sh >= 0 && d_sh <= d, "d_shared must be in 0..d");
+  const int64_t d_sa = d - d_sh;
+  ARGCHECK(d_sh == 0 || v_sh, "null v_shared with d_shared > 0");
+  ARGCHECK(d_sa == 0 || v_sa, "null v_samp with d - d_shared > 0");
+  ARGCHECK(d_sh == 0 || ldvs >= d_sh, "ldvs must be >= d_shared");
+  ARGCHECK(d_sa == 0 || (ld_r >= d_sa && ld_s >= (n_star - 1) * ld_r + d_sa),
+           "sample strides: ld_r must be >= d - d_shared and ld_s >= (n_star - 1) ld_r + d - d_shared");
+  ARGCHECK(ldf_r >= 1 && ldf_s >= (n_star - 1) * ldf_r + 1,
+           "output strides: ldf_r must be >= 1 and ldf_s >= (n_star - 1) ldf_r + 1");
+  ARGCHECK(samples >= 1 && samples <= kMaxSamples, "samples must be in 1..65536");
+}
 // Device bytes of a prediction's workspace (what gpar_fit_predict reserves beside the fit's cache)
 int64_t predict_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d, int mode,
                             int samples, bool fused);
 int64_t predict_mean_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d);
+// host: the sample inputs and the delivered samples are staged on the device too
+int64_t predict_samples_ws_estimate(int64_t n, int64_t n_star, int64_t mp, int64_t d_sh,
+                                    int64_t d_sa, int samples, bool host);
 
 }  // namespace gpar

@@ -304,6 +304,24 @@ void launch_mean_finish(hipStream_t st, int sdim, const double* u, const double*
                         const double* fstar, const int64_t* pos, int64_t nstar, int L,
                         double* mean);
 
+// k_kfu_samples.hip (sample-chained prediction)
+// FX[pos[i] * ldfx + s] = sum_c s_o kappa(|[vsh_i , vsa_{s,i}] - z_c| / l_o) Bm[s * ldb + c] for the
+// nstar test rows and S samples, no kernel matrix stored: vsh nstar x d_sh (ld ldvs) shared by the
+// samples, sample element (s, i, q) at vsa[s * ld_s + perm[i] * ld_r + q] (perm null: identity),
+// d_sh + d_sa = the problem's d, either may be 0 (its pointer then unused)
+void launch_kfu_samples(hipStream_t st, int out_kind, const double* vsh, int64_t ldvs, int d_sh,
+                        const double* vsa, int64_t ld_s, int64_t ld_r, int d_sa,
+                        const int64_t* perm, int64_t nstar, int S, const double* z, int64_t ldz,
+                        int64_t m, const double* zc, const double* Bm, int64_t ldb, double inv_lo,
+                        double s_o, const int64_t* pos, double* FX, int64_t ldfx);
+// dst[pos[k] * ldd + s] = src[k * S + s], k < n
+void launch_scatter_rows(hipStream_t st, const double* src, int64_t n, int S, const int64_t* pos,
+                         double* dst, int64_t ldd);
+// out[s * ld_s + i * ld_r] = fx[pos[i] * ldfx + s] + F[pos[i] * S + s]: the samples path_stats reduces
+void launch_sample_values(hipStream_t st, const double* fx, int64_t ldfx, const double* F, int S,
+                          const int64_t* pos, int64_t nstar, double* out, int64_t ld_s,
+                          int64_t ld_r);
+
 // k_kmeans.hip (pseudo-input selection: Lloyd's k-means, layouts in the file header)
 // g[i] = mean over the m centres of z[c][i], i < d (the centre the assignment's Gram form is
 // taken about)

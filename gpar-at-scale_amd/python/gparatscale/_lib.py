@@ -31,6 +31,7 @@ EXPORTED = (
     "gpar_predict_mean", "gpar_posterior_predict_mean", "gpar_posterior_prepare_mean",
     "gpar_nm_create", "gpar_nm_destroy", "gpar_nm_ask", "gpar_nm_tell", "gpar_nm_result",
     "gpar_select_pseudo_inputs",
+    "gpar_predict_samples", "gpar_posterior_predict_samples",
 )
 
 
@@ -131,6 +132,10 @@ def load(path: str | None = None):
             "gpar_predict_mean": (i32, [vp, C.POINTER(GparProblem), dp, i64, dp, dp, i64, dp]),
             "gpar_posterior_predict_mean": (i32, [vp, vp, i32, i64, vp, vp, i64, vp]),
             "gpar_posterior_prepare_mean": (i32, [vp, vp, i32, i64, vp]),
+            "gpar_predict_samples": (i32, [vp, C.POINTER(GparProblem), dp, i64, dp, dp, i64, i64, dp,
+                                           i64, i64, i32, C.c_uint64, dp, i64, i64, dp, dp]),
+            "gpar_posterior_predict_samples": (i32, [vp, vp, i32, i64, vp, vp, i64, i64, vp, i64,
+                                                     i64, i32, C.c_uint64, vp, i64, i64, vp, vp]),
             "gpar_mc_normals": (i32, [vp, i32, i64, C.c_uint64, dp]),
             "gpar_path_normals": (i32, [vp, i32, i64, i32, C.c_uint64, dp]),
             "gpar_lgssm_posterior_rand": (i32, [vp, i64, dp, dp, dp, i32, dp, i32, C.c_uint64, i32, dp]),

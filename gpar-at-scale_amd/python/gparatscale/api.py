@@ -524,6 +524,119 @@ def get_gpar_scaled_predictions_batch(Y, pseudo_input_locations, time_loc, infer
     return FitResult(theta, nlml, evals), means, stds
 
 
+def _samples_call(call, dev, d, t_star, shared_inputs, sample_inputs, samples, seed, out, device):
+    """Marshalling of gpar_predict_samples / gpar_posterior_predict_samples (their arguments after
+    the problem or posterior): `call(n_star, t_star, v_shared, ldvs, d_shared, v_samp, ld_s, ld_r,
+    samples, seed, f_out, ldf_s, ldf_r, mean, std)` makes the library call.  Everything the C side
+    cannot see (lengths, widths, strides of tensors) is checked here.  Returns (F, mean, std)."""
+    keep = _Keep()
+    ctx = context(device)
+    if samples is None:
+        samples = sample_inputs.shape[0] if sample_inputs is not None else 100
+    S = int(samples)
+    if sample_inputs is not None and (len(sample_inputs.shape) != 3 or sample_inputs.shape[0] != S):
+        raise _arg_error("sample_inputs must be samples x N* x d_sa")
+    if dev:
+        import torch
+        if not _is_torch(t_star):
+            raise _arg_error("device problems take device tensors")
+        ns = t_star.numel()
+        tsp = _dev_vec(t_star, keep)
+        vshp, ldvs, d_sh = None, 0, 0
+        if shared_inputs is not None and shared_inputs.numel():
+            vshp, ldvs, nr, d_sh = _dev_points(shared_inputs, keep)
+            if nr != ns:
+                raise _arg_error("shared_inputs must be N* x d_sh with N* = len(t_star)")
+        vsap, ld_s, ld_r, d_sa = None, 0, 0, 0
+        if sample_inputs is not None and sample_inputs.shape[2]:
+            X = sample_inputs
+            if X.dtype != torch.float64:
+                raise _arg_error("float64 tensors required")
+            if X.stride(2) != 1:
+                X = X.contiguous()
+            keep.append(X)
+            if X.shape[1] != ns:
+                raise _arg_error("sample_inputs must be samples x N* x d_sa with N* = len(t_star)")
+            vsap, ld_s, ld_r, d_sa = X.data_ptr(), X.stride(0), X.stride(1), X.shape[2]
+        if sample_inputs is not None and d_sh + d_sa != d:
+            raise _arg_error(f"shared ({d_sh}) and sample ({d_sa}) input columns must add up to D = {d}")
+        if out is None:
+            out = torch.empty((max(S, 0), ns), dtype=torch.float64, device=t_star.device)
+        elif (not _is_torch(out) or out.dtype != torch.float64 or tuple(out.shape) != (S, ns)):
+            raise _arg_error("out must be a float64 samples x N* device tensor (any strides)")
+        mean = torch.empty(ns, dtype=torch.float64, device=t_star.device)
+        std = torch.empty(ns, dtype=torch.float64, device=t_star.device)
+        with _after_torch(ctx):
+            ctx.check(call(ns, tsp, vshp, ldvs, d_sh, vsap, ld_s, ld_r, S, int(seed), out.data_ptr(),
+                           out.stride(0) if S > 1 else max(out.stride(0), (ns - 1) * out.stride(1) + 1),
+                           out.stride(1) if ns > 1 else 1, mean.data_ptr(), std.data_ptr()))
+        return out, mean, std
+    ns = len(np.asarray(t_star))
+    tsp = _host_vec(t_star, keep)
+    vshp, ldvs, d_sh = None, 0, 0
+    if shared_inputs is not None and np.size(shared_inputs):
+        vshp, ldvs, nr, d_sh = _host_points(shared_inputs, keep)
+        if nr != ns:
+            raise _arg_error("shared_inputs must be d_sh x N* with N* = len(t_star)")
+    vsap, ld_s, ld_r, d_sa = None, 0, 0, 0
+    if sample_inputs is not None and sample_inputs.shape[2]:
+        X = sample_inputs
+        # read in place when it is a float64 array with unit last stride (a column prefix of a wider
+        # S x N* x K array included), else through a packed copy
+        if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.strides[2] == 8
+                and X.strides[0] % 8 == 0 and X.strides[1] % 8 == 0
+                and X.strides[1] >= 8 * X.shape[2]
+                and X.strides[0] >= (X.shape[1] - 1) * X.strides[1] + 8 * X.shape[2]):
+            X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+        keep.append(X)
+        if X.shape[1] != ns:
+            raise _arg_error("sample_inputs must be samples x N* x d_sa with N* = len(t_star)")
+        vsap, ld_s, ld_r, d_sa = X.ctypes.data, X.strides[0] // 8, X.strides[1] // 8, X.shape[2]
+    if sample_inputs is not None and d_sh + d_sa != d:
+        raise _arg_error(f"shared ({d_sh}) and sample ({d_sa}) input columns must add up to D = {d}")
+    if out is None:
+        out = np.zeros((max(S, 0), ns))
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (S, ns)
+              and out.flags.writeable and out.strides[0] % 8 == 0 and out.strides[1] % 8 == 0
+              and out.strides[1] > 0 and out.strides[0] > 0):
+        raise _arg_error("out must be a writable float64 samples x N* array (positive strides)")
+    mean, std = np.zeros(ns), np.zeros(ns)
+    ldf_r = out.strides[1] // 8 if ns > 1 else 1
+    ldf_s = out.strides[0] // 8 if S > 1 else max(out.strides[0] // 8, (ns - 1) * ldf_r + 1)
+    ctx.check(call(ns, tsp, vshp, ldvs, d_sh, vsap, ld_s, ld_r, S, int(seed), out.ctypes.data, ldf_s,
+                   ldf_r, _ptr(mean), _ptr(std)))
+    return out, mean, std
+
+
+def predict_samples_scaled(input_locations, pseudo_input_locations, time_loc, outputs, theta,
+                           inference_time_loc, shared_inputs, sample_inputs, samples=None, seed=0,
+                           out=None, out_kernel="matern52", time_kernel="matern52", device=0,
+                           qu_kuu_noise=False):
+    """Joint samples of one output at the inference locations when every sample has inference
+    inputs of its own (gpar_predict_samples): predict_scaled's mode="path" -- a q(u) draw and a
+    posterior path of the time GP per sample -- with sample s's kernel matrix taken at
+    [shared_inputs | sample_inputs[s]].  GPAR's joint draws feed sample s of the earlier outputs
+    into sample s of this one that way.  The draws are mode="path"'s for (samples, seed)
+    (mc_normals, path_normals), so with no sample columns this is mode="path" with its samples.
+
+    Host problems: shared_inputs d_sh x N* (ColVecs; None or empty: no shared columns),
+    sample_inputs an S x N* x d_sa array (None: no sample columns).  Device problems: N* x d_sh and
+    S x N* x d_sa tensors with unit last stride; a column-prefix view of a wider S x N* x K tensor
+    is read in place.  d_sh + d_sa = D.  samples: S (default: sample_inputs' first dimension).
+    out: an S x N* view, possibly strided, to write the samples into -- it may be a column of the
+    tensor sample_inputs is a prefix of, which is how a chain of outputs is sampled in place.
+
+    Returns (F, mean, std): F S x N* (out when given), mean and Bessel std over the samples, all at
+    the inference locations in their input order (samples = 1: std is NaN)."""
+    p, keep = make_problem(input_locations, pseudo_input_locations, time_loc, outputs,
+                           out_kernel, time_kernel, qu_kuu_noise=qu_kuu_noise)
+    th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(5))
+    ctx, lib = context(device), _lib.load()
+    call = lambda *a: lib.gpar_predict_samples(ctx.h, C.byref(p), _ptr(th), *a)
+    return _samples_call(call, p.mem == _lib.GPAR_MEM_DEVICE, p.d, inference_time_loc,
+                         shared_inputs, sample_inputs, samples, seed, out, device)
+
+
 class Posterior:
     """gpar_fit_posterior's result: the fitted theta of every output and its q(u), kept on the
     device, so that predictions whose inference inputs arrive later (the chained sweep of
@@ -600,6 +713,59 @@ class Posterior:
         ctx.check(lib.gpar_posterior_predict_mean(ctx.h, self.h, int(i), ns,
                                                   _host_vec(t_star, keep), vsp, ldvs, _ptr(mean)))
         return mean
+
+    def predict_samples(self, i, t_star, shared_inputs, sample_inputs, samples=None, seed=0,
+                        out=None):
+        """Output i's joint samples at per-sample inference inputs (gpar_posterior_predict_samples;
+        arguments, layouts and the returned (F, mean, std) as predict_samples_scaled's).  Uses and
+        consumes a matching prepare(i, t_star)."""
+        if not 0 <= int(i) < len(self._problems):
+            raise _arg_error(f"output index {i} out of range (0..{len(self._problems) - 1})")
+        p = self._problems[i]
+        ctx, lib = context(self.device), _lib.load()
+        call = lambda *a: lib.gpar_posterior_predict_samples(ctx.h, self.h, int(i), *a)
+        dev = p.mem == _lib.GPAR_MEM_DEVICE
+        try:
+            return _samples_call(call, dev, p.d, t_star, shared_inputs, sample_inputs, samples, seed,
+                                 out, self.device)
+        finally:
+            if dev:   # the prepared slot is consumed (stream-ordered before any later use)
+                self._prepared.pop(int(i), None)
+
+    def sample_chain(self, t_star, given_inputs, samples, seed=0):
+        """Joint samples of all outputs of a GPAR-ordered posterior -- output i's inputs are the
+        d_given given columns followed by outputs 0..i-1, D_i = d_given + i -- at t_star: the chain
+        p(y_0 | x) p(y_1 | x, y_0) ... sampled jointly, sample s of the earlier outputs feeding
+        sample s of the later ones.  given_inputs: d_given x N* (host, ColVecs) / N* x d_given
+        (device).  Allocates the S x N* x P chain tensor and sweeps the outputs in order: output i
+        reads columns [:i] of every sample's slab in place, draws with seed + i (fit_predict_batch's
+        convention) and writes column i.  Returns (samples S x N* x P, means, stds), means / stds
+        lists of the per-output sample mean and Bessel std.  One rank only."""
+        P = len(self._problems)
+        S = int(samples)
+        dev = self._problems[0].mem == _lib.GPAR_MEM_DEVICE
+        if dev:
+            import torch
+            ns = t_star.numel()
+            given = given_inputs.reshape(ns, -1) if given_inputs.dim() == 1 else given_inputs
+            dg = given.shape[1]
+            chain = torch.empty((max(S, 0), ns, P), dtype=torch.float64, device=t_star.device)
+        else:
+            ns = len(np.asarray(t_star))
+            given = to_colvecs(given_inputs)
+            dg = given.shape[0]
+            chain = np.zeros((max(S, 0), ns, P))
+        for i, p in enumerate(self._problems):
+            if p.d != dg + i:
+                raise _arg_error(f"sample_chain: output {i} must have D = d_given + {i} = {dg + i} "
+                                 f"inputs, has {p.d}")
+        means, stds = [], []
+        for i in range(P):
+            _, m, s = self.predict_samples(i, t_star, given, chain[:, :, :i] if i else None,
+                                           samples=S, seed=int(seed) + i, out=chain[:, :, i])
+            means.append(m)
+            stds.append(s)
+        return chain, means, stds
 
     def prepare(self, i, t_star):
         """Queue output i's inference-input-independent prediction work for device test times

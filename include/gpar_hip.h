@@ -343,6 +343,35 @@ int32_t gpar_predict_mean(gpar_ctx* ctx, const gpar_problem* prob, const double*
                           int64_t n_star, const double* t_star, const double* v_star,
                           int64_t ldvs, double* mean);
 
+/* Sample-chained prediction: GPAR_PREDICT_PATH with test inputs of each sample's own, the samples
+ * returned.  GPAR's predictive distribution is the chain p(y1|x) p(y2|x, y1) ...: a joint draw of
+ * the outputs feeds sample s of the earlier outputs into sample s of this one, which gpar_predict
+ * (one v_star for all samples) cannot express.  Test point k of sample s sits at the input
+ *   [ v_shared[k*ldvs + 0 .. d_shared) , v_samp[s*ld_s + k*ld_r + 0 .. d - d_shared) ]
+ * (d = prob->d; d_shared in 0..d; either part may be empty, its pointer then unused).  Per sample:
+ * a q(u) draw, f_x,s = Cf*u,s U_u^{-1} e_s with Cf*u,s at the sample's own test inputs (never
+ * stored; the training rows use the training inputs), a posterior path of the time GP given
+ * y* - f_x,s, f*_s = f_x,s + f_t,s.  The draws are exactly GPAR_PREDICT_PATH's for (samples, seed) --
+ * gpar_mc_normals(samples, m, seed) and gpar_path_normals(samples, n + n_star, D + 1, seed) -- so
+ * with d_shared = d the call is gpar_predict's PATH mode with its samples exposed.
+ * f_out[s*ldf_s + k*ldf_r]: sample s at test point k, in the caller's order of t_star.  mean, std
+ * [n_star] (either may be NULL): the sample mean and Bessel-corrected std over the samples, as
+ * PATH mode reduces them (samples = 1: the std is 0/0, NaN).  samples in 1..65536.  All pointers in
+ * prob->mem; device t_star ascending, as for gpar_predict.
+ * f_out may point into the tensor v_samp points into, at a column this call does not read (for
+ * instance v_samp = chain, f_out = chain + d - d_shared, ldf_s = ld_s, ldf_r = ld_r in a samples x
+ * n_star x K tensor): every input is read before anything is written, which is how a chain of
+ * outputs is sampled in place.  GPAR_ERR_ARG for d_shared outside 0..d, a NULL v_samp with
+ * d_shared < d (a NULL v_shared with d_shared > 0), ldvs < d_shared, ld_r < d - d_shared, ld_s <
+ * (n_star - 1) ld_r + d - d_shared, ldf_r < 1, ldf_s < (n_star - 1) ldf_r + 1, samples < 1;
+ * GPAR_ERR_UNSUPPORTED for the time kernel EQ (as gpar_lgssm_posterior_rand).  Event-timing family
+ * "pred_sfx": the per-sample Cf*u product (gpar_ctx_kernel_work: flops, 2 samples n_star m d). */
+int32_t gpar_predict_samples(gpar_ctx* ctx, const gpar_problem* prob, const double* theta,
+                             int64_t n_star, const double* t_star, const double* v_shared,
+                             int64_t ldvs, int64_t d_shared, const double* v_samp, int64_t ld_s,
+                             int64_t ld_r, int32_t samples, uint64_t seed, double* f_out,
+                             int64_t ldf_s, int64_t ldf_r, double* mean, double* std);
+
 /* The standard-normal draws MC mode uses for (samples, m, seed): xi_out[s*m + j] is the j-th
  * coordinate of draw s (host, samples x m).  The m_e sample of draw s is m_e + chol(inv(D)).L
  * xi_s, as Distributions' rand(MvNormal(m_e, Symmetric(inv(D)))) maps a standard-normal vector
@@ -440,6 +469,15 @@ int32_t gpar_posterior_predict_mean(gpar_ctx* ctx, const gpar_posterior* post, i
  * rules and t_star lifetime rule; either predict call may consume the slot. */
 int32_t gpar_posterior_prepare_mean(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
                                     int64_t n_star, const double* t_star);
+/* gpar_predict_samples from a posterior object: output i's samples at per-sample inference inputs
+ * (same arguments; d = output i's input dimension).  Uses a matching slot of
+ * gpar_posterior_prepare if there is one (and consumes it), with bit-identical results. */
+int32_t gpar_posterior_predict_samples(gpar_ctx* ctx, const gpar_posterior* post, int32_t i,
+                                       int64_t n_star, const double* t_star,
+                                       const double* v_shared, int64_t ldvs, int64_t d_shared,
+                                       const double* v_samp, int64_t ld_s, int64_t ld_r,
+                                       int32_t samples, uint64_t seed, double* f_out,
+                                       int64_t ldf_s, int64_t ldf_r, double* mean, double* std);
 int32_t gpar_posterior_destroy(gpar_posterior* post);
 
 /* ---------------------------------------------------------------- temporal-only (LGSSM) chains

@@ -19,6 +19,10 @@ and the chooser of pseudo-inputs the reference leaves to its caller (k-means on 
 
   select_pseudo_inputs               -> (Z, index, labels, counts, inertia)
 
+and joint samples of an output whose inference inputs differ per sample (GPAR's chained draws):
+
+  get_gpar_scaled_prediction_samples -> (F, means, stds)
+
 with every number computed by the gfx950 kernels behind include/gpar_hip.h.  A caller switches
 `using GPARatScale` to `using GPARatScale, GPARatScaleHIP` and qualifies these five names (or
 imports them from GPARatScaleHIP).  The reference's helpers (to_ColVecs, unpack_gpar,
@@ -43,7 +47,7 @@ using GPARatScale: to_ColVecs, unpack_gpar, unpack_gp, parse_initial_gpar_params
 
 export compute_gpar_dtc_objective, get_optim_scaled_gpar_params, compute_q_u,
        get_gpar_scaled_predictions, get_sde_predictions, get_gpar_scaled_predictions_batch,
-       select_pseudo_inputs
+       select_pseudo_inputs, get_gpar_scaled_prediction_samples
 
 const libgpar = get(ENV, "GPAR_HIP_LIB", "libgparhip.so")
 
@@ -324,6 +328,62 @@ function get_gpar_scaled_predictions(input_locations, pseudo_input_locations, ti
         end
     end
     return means, stds
+end
+
+# ------------------------------------------------------------------ sample-chained prediction
+"""
+    get_gpar_scaled_prediction_samples(input_locations, pseudo_input_locations, time_loc, outputs,
+                                       theta, inference_time_loc, shared_inference_inputs,
+                                       sample_inference_inputs; samples, seed,
+                                       out_kernel_structure, time_kernel_structure)
+
+Joint samples of one output at `theta` (natural units, as get_optim_scaled_gpar_params returns it)
+when every sample has inference inputs of its own: the path estimator of tmp.jl:119-167 (a q(u)
+draw and a posterior_rand path per sample) with sample s's Cf*u taken at
+[shared_inference_inputs | sample_inference_inputs[:, :, s]] -- how a joint draw of GPAR's outputs
+feeds sample s of the earlier outputs into sample s of a later one.  `shared_inference_inputs`:
+what to_ColVecs takes (d_sh dimensions, N* points) or `nothing`; `sample_inference_inputs`: a
+d_sa x N* x S array (slice s = sample s's ColVecs matrix) or `nothing`; d_sh + d_sa = D.
+Returns (F, means, stds): F an N* x S matrix (column s = sample s at the inference locations),
+means / stds the sample mean and Bessel-corrected std (one sample: NaN stds).
+"""
+function get_gpar_scaled_prediction_samples(input_locations, pseudo_input_locations, time_loc,
+        outputs, theta, inference_time_loc, shared_inference_inputs, sample_inference_inputs;
+        samples::Integer = sample_inference_inputs === nothing ? 100 : size(sample_inference_inputs, 3),
+        seed::UInt64 = rand(UInt64),
+        out_kernel_structure = Matern52(), time_kernel_structure = Matern52())
+    V = _colmat(input_locations)
+    Z = _colmat(pseudo_input_locations)
+    t = Vector{Float64}(time_loc)
+    y = Vector{Float64}(outputs)
+    ts = Vector{Float64}(inference_time_loc)
+    ns = length(ts)
+    θ = Float64[theta...]
+    length(θ) == 5 || throw(DomainError(length(θ), "theta must hold 5 values"))
+    Vsh = shared_inference_inputs === nothing ? zeros(0, ns) : _colmat(shared_inference_inputs)
+    Vsa = sample_inference_inputs === nothing ? zeros(0, ns, samples) :
+          Array{Float64,3}(sample_inference_inputs)
+    size(Vsh, 2) == ns || throw(DomainError(size(Vsh, 2), "shared inference inputs need N* points"))
+    size(Vsa, 2) == ns && size(Vsa, 3) == samples ||
+        throw(DomainError(size(Vsa), "sample inference inputs must be d_sa x N* x samples"))
+    dsh, dsa = size(Vsh, 1), size(Vsa, 1)
+    dsh + dsa == size(V, 1) || throw(DomainError(dsh + dsa, "d_sh + d_sa must equal D"))
+    F = zeros(ns, samples)
+    means = zeros(ns)
+    stds = zeros(ns)
+    c = ctx()
+    GC.@preserve V Z t y ts θ Vsh Vsa F means stds begin
+        p = Ref(problem(V, Z, t, y, out_kernel_structure, time_kernel_structure))   # GPAR_MEM_HOST
+        check(c, ccall((:gpar_predict_samples, libgpar), Int32,
+                       (Ptr{Cvoid}, Ref{GparProblem}, Ptr{Float64}, Int64, Ptr{Float64},
+                        Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Int32, UInt64,
+                        Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                       c.h, p, θ, ns, ts, dsh == 0 ? C_NULL : pointer(Vsh), Int64(max(dsh, 1)),
+                       Int64(dsh), dsa == 0 ? C_NULL : pointer(Vsa), Int64(max(dsa, 1) * ns),
+                       Int64(max(dsa, 1)), Int32(samples), seed, F, Int64(ns), Int64(1), means,
+                       stds))
+    end
+    return F, means, stds
 end
 
 # ------------------------------------------------------------------ the GPAR per-output driver loop
