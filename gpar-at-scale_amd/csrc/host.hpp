@@ -24,6 +24,7 @@
 #include "launch.hpp"
 #include "nelder_mead.hpp"
 #include "nm_dev.hpp"
+#include "span.hpp"
 
 namespace gpar {
 struct PredPrep;
@@ -102,7 +103,9 @@ struct gpar_ctx {
   // fit with a wall-clock time limit)
   int device_nm = 1;
   // "dg_rows_w": percent more rows per DG split on the whitening CUs (fewer on the Gram CUs);
-  // kDgRowsAuto: +40 in the round-by-round fit, where the whitening side (3.19 ms whitening since
+  // kDgRowsAuto: +30 in the round-by-round fit when corr_span leaves the Gram CUs less correction
+  // work (north, S = 2: 16.79 s per job at +30, 16.91 at +40, 17.30 at +50,
+  // profiles/ab_corr_span.txt), else +40 in the round-by-round fit, where the whitening side (3.19 ms whitening since
   // the DPP step rows, r05r) has time to spare and the Gram CUs' side sets the span (north, same
   // box, 3 pairs: 5.074 ms per Gram / 17.584 s per job at +10 with the r05p whitening, 5.012 ms /
   // 17.384 s at +40; +60: 5.25 ms), +20 in the round overlap, whose whitening side also runs the
@@ -114,6 +117,15 @@ struct gpar_ctx {
   // evaluation runs its whitening and Gram.  A plan like dg_rows_w: bit-identical to its
   // serialized twin, within rounding of 0.
   int scaled_gram = 1;
+  // "corr_span": chunks per span of the batched fit's cached whitening (whiten_kfu_d2x2), 1 / 2 /
+  // 4 / 8, -1 = auto (span.hpp: kCorrSpanAuto in fit calls of at least kCorrSpanAutoMinOutputs
+  // outputs that take the CU split by its size gate -- the round-by-round split fit, where it was
+  // measured faster -- else 1).  The filter state is reset once per span, so the Gram's chunk correction, the carry
+  // of beta's columns and vec_fix's E_j / q_j run over ceil(nch / S) spans (k_span.hip).  Applies
+  // to the outputs eval_dtc whitens from the distance cache in its per-output Gram schedules
+  // (job_span, host_objective.cpp); 1 is the one-chunk code path.  A plan: bit-identical to its
+  // serialized twin, within rounding of 1.
+  int corr_span = -1;
   // "chain_mean_first": gpar_fit_predict_chain (device memory, ANALYTIC) runs only each output's
   // mean-only prediction (predict_mean_impl) in chain order on the context stream; the full
   // predictions, which supply the stds, follow on the side stream's lane.  0 (default): the full
@@ -121,6 +133,7 @@ struct gpar_ctx {
   // of 0's); bit-identical to its serialized twin.
   int chain_mean_first = 0;
   gpar::ScaledGram* sgram = nullptr;   // the running fit call's slots (fit_impl), else null
+  int fit_outputs = 0;                 // outputs of the running fit call (fit_impl), else 0
   // "serialize": side, s_w, s_g, s_g2 and s_d all alias `main`, so every launch runs in issue order
   // on one stream (the created streams stay in own_*): the order-free reference the concurrent
   // schedule must equal bit for bit.  Plans, CU shares of work items and workspaces are unchanged.
@@ -282,6 +295,8 @@ inline int64_t round_up(int64_t x, int64_t q) { return ((x + q - 1) / q) * q; }
 void run_carry(gpar_ctx* c, int sdim, const double* phi, int64_t phistride,
                       const double* send, double* cin, int64_t sstride, int64_t nch, int64_t mc,
                       int64_t ncols, int nchains, const std::string& tag, bool rev = false);
+void reserve_carry(gpar_ctx* c, int sdim, int64_t nch, int64_t mc, int nchains,
+                   const std::string& tag);
 
 // --------------------------------------------------------------------------- problems on device
 struct DevProblem {
@@ -304,6 +319,20 @@ struct DevProblem {
 inline const double* cached_d2(const gpar_ctx* c, const DevProblem& p) {
   if (!p.d2 || p.cache_slot < 0 || p.cache_slot >= (int)c->cache_valid.size()) return nullptr;
   return c->cache_valid[p.cache_slot] ? p.d2 : nullptr;
+}
+// Chunks per span of an output's whitening under gpar_ctx::corr_span, in a batch of widest padded
+// width mpmax that does (split) or does not take the CU split: only the cached whitening walks
+// spans.  One rule for the round-by-round stage (GramStage::job_span) and the round overlap on the
+// split (fit_overlapped), which must agree bit for bit: so auto goes by the size of the fit call,
+// not by which of the two schedules runs it.  Calls of up to 16 outputs (the round overlap's auto
+// range, one rank's shard of the north job) keep 1: there the span measured within the spread of
+// the parent's own runs (profiles/ab_corr_span.txt, table 7).
+constexpr int kCorrSpanAutoMinOutputs = 17;
+inline int cached_job_span(const gpar_ctx* c, const DevProblem& p, bool split, int64_t mpmax) {
+  if (!cached_d2(c, p)) return 1;
+  const bool big = (double)p.n * (double)mpmax * (double)mpmax >= kSplitMinWork &&
+                   c->fit_outputs >= kCorrSpanAutoMinOutputs;
+  return corr_span_resolve(c->corr_span, split, big);
 }
 bool shares_grid(const std::vector<DevProblem>& P);
 bool fit_pipelined(const gpar_ctx* c, const std::vector<DevProblem>& P, bool fix_beta = false);
@@ -403,7 +432,8 @@ GainsOut run_gains(gpar_ctx* c, int sdim, const double* t, int64_t n,
 // d2_in_beta: the caller already wrote the distances into beta (a separately timed pass)
 void whiten_kfu_any(gpar_ctx* c, const DevProblem& p, const GainsOut& gi, const double* v,
                            int64_t ldv, int64_t n, int64_t nch, const Theta& th, double* beta,
-                           int64_t ldb, double* send, double* hsum, bool d2_in_beta = false);
+                           int64_t ldb, double* send, double* hsum, bool d2_in_beta = false,
+                           int span = 1, const double* psi_pre = nullptr);
 
 // --------------------------------------------------------------------------- Gram stage
 struct GramOut {
@@ -417,6 +447,9 @@ struct GramOut {
 struct StageBufs {
   int idx;   // 0 / 1: workspace names, carry tags
   double *beta, *alpha, *send, *cin, *hsum, *qv;
+  // corr_span > 1: Psi_i per chunk and per span (span_psi_kernel), alpha's own chunk states
+  // (stage_bufs only; null in the grouped Gram's per-slot buffers, which never take a span)
+  double *psi_pre = nullptr, *psi_span = nullptr, *acin = nullptr;
 };
 StageBufs stage_bufs(gpar_ctx* c, int l, int64_t n, int64_t mpmax);
 
@@ -436,6 +469,8 @@ struct StageJob {
   int group = -1;
   bool last = false;
   hipEvent_t* after = nullptr;
+  // chunks per span of this job's whitening, short chain and Gram correction ("corr_span")
+  int span = 1;
 };
 void stage_whiten(gpar_ctx* c, const StageJob& j, const StageBufs& b);
 void stage_post(gpar_ctx* c, const StageJob& j, const StageBufs& b, bool fix_beta);

@@ -109,6 +109,7 @@ static constexpr Knob kKnobs[] = {
     {"fit_chunks", &gpar_ctx::fit_chunks, -1, 4096, 0},
     {"device_nm", &gpar_ctx::device_nm, 0, 1, 0},
     {"chain_mean_first", &gpar_ctx::chain_mean_first, 0, 1, 0, true},
+    {"corr_span", &gpar_ctx::corr_span, 1, kMaxCorrSpan, -1},
 };
 static const Knob* find_knob(const std::string& k) {
   for (const Knob& kn : kKnobs)
@@ -122,6 +123,7 @@ static int set_schedule(gpar_ctx* c, const std::string& k, int v) {
   if (!kn) return GPAR_ERR_ARG;
   if (kn->flag) v = v != 0;
   else if ((v < kn->lo || v > kn->hi) && v != kn->extra) return GPAR_ERR_ARG;
+  if (kn->field == &gpar_ctx::corr_span && v != kn->extra && !corr_span_valid(v)) return GPAR_ERR_ARG;
   if (kn->field == &gpar_ctx::serialize) {
     // the streams about to be re-routed must not hold queued work
     (void)hipStreamSynchronize(c->main);
@@ -270,6 +272,33 @@ int64_t gpar_debug_counter(const char* name) {
   if (std::strcmp(name, "gains_p1_lane1") == 0) return g_gains_p1_lane1_launches.load();
   if (std::strcmp(name, "gains_p1_lane4") == 0) return g_gains_p1_lane4_launches.load();
   return -1;
+}
+
+int32_t gpar_corr_span_plan(int32_t knob, int32_t split, int32_t outputs, int64_t n, int64_t mp,
+                            int32_t* span, int64_t* nspans) {
+  if (!span || !nspans || n < 1 || mp < 1 || outputs < 1) return GPAR_ERR_ARG;
+  if (knob != -1 && !corr_span_valid(knob)) return GPAR_ERR_ARG;
+  const bool big = (double)n * (double)mp * (double)mp >= kSplitMinWork &&
+                   outputs >= kCorrSpanAutoMinOutputs;
+  *span = corr_span_resolve(knob, split != 0, big);
+  *nspans = span_count((n + kChunk - 1) / kChunk, *span);
+  return GPAR_OK;
+}
+
+int32_t gpar_corr_span_psi(int32_t sdim, int64_t nch, int32_t span, const double* phi, double* pre,
+                           double* tot) {
+  if (sdim < 1 || sdim > 3 || nch < 1 || !corr_span_valid(span) || !phi || !pre || !tot)
+    return GPAR_ERR_ARG;
+  const int dd = sdim * sdim;
+  for (int64_t J = 0, j0 = 0; j0 < nch; ++J, j0 += span) {
+    const int cnt = (int)(j0 + span <= nch ? span : nch - j0);
+    switch (sdim) {
+      case 1: span_psi<1>(phi + j0 * dd, cnt, pre + j0 * dd, tot + J * dd); break;
+      case 2: span_psi<2>(phi + j0 * dd, cnt, pre + j0 * dd, tot + J * dd); break;
+      default: span_psi<3>(phi + j0 * dd, cnt, pre + j0 * dd, tot + J * dd); break;
+    }
+  }
+  return GPAR_OK;
 }
 
 int32_t gpar_ctx_set_input_stream(gpar_ctx* ctx, void* stream, int32_t enable) {

@@ -100,6 +100,17 @@ void h2d_rows(gpar_ctx* c, double* dst, const double* src, int64_t ld, int64_t w
 }
 
 // Two-level carry over chunks (k_lgssm.hip launch_carry) with context workspace.
+// run_carry's scratch under `tag` for a carry over nch chunks, taken ahead of time (the workspace
+// only grows, so the later run_carry finds it in place).
+void reserve_carry(gpar_ctx* c, int sdim, int64_t nch, int64_t mc, int nchains,
+                   const std::string& tag) {
+  const int gs = carry_group_size(nch);
+  const int64_t ng = (nch + gs - 1) / gs;
+  (void)ws<double>(c, tag + "_gend", (size_t)nchains * ng * mc * 4);
+  (void)ws<double>(c, tag + "_gin", (size_t)nchains * ng * mc * 4);
+  (void)ws<double>(c, tag + "_psi", (size_t)nchains * ng * sdim * sdim);
+}
+
 void run_carry(gpar_ctx* c, int sdim, const double* phi, int64_t phistride,
                       const double* send, double* cin, int64_t sstride, int64_t nch, int64_t mc,
                       int64_t ncols, int nchains, const std::string& tag, bool rev) {

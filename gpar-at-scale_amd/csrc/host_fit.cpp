@@ -229,6 +229,8 @@ static void run_groups(std::vector<Group>& grp, const Finish& finish, const Begi
 // that work over the round.  Auto (overlap_group 0): groups of kOverlapGroupAuto in calls of up to
 // kOverlapMaxOutputs outputs; larger calls keep the round-by-round schedule.
 constexpr int kOverlapMaxOutputs = 16;
+static_assert(kCorrSpanAutoMinOutputs == kOverlapMaxOutputs + 1,
+              "corr_span auto: the calls the round overlap does not take by size");
 constexpr int kOverlapGroupAuto = 8;
 
 struct OverlapGroup : RoundGroup {
@@ -381,6 +383,7 @@ static void fit_overlapped(gpar_ctx* c, const std::vector<DevProblem>& P,
       j.ldg = mpmax;
       j.group = G.id;
       j.last = a == na - 1;
+      j.span = cached_job_span(c, G.sub[a], true, mpmax);   // as the round-by-round stage (overlap 0)
       sp.push(j);
     }
     G.in_flight = true;
@@ -652,8 +655,12 @@ void fit_impl(gpar_ctx* ctx, const std::vector<DevProblem>& P0, const double* lo
   ScaledGram sgram;
   struct SgramScope {
     gpar_ctx* c;
-    ~SgramScope() { c->sgram = nullptr; }
+    ~SgramScope() {
+      c->sgram = nullptr;
+      c->fit_outputs = 0;
+    }
   } sgram_scope_{ctx};
+  ctx->fit_outputs = nprob;
   if (ctx->scaled_gram) {
     for (int i = 0; i < nprob; ++i) P[i].fit_idx = i;
     sgram.slot.assign(nprob, {});

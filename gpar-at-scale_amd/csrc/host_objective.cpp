@@ -11,7 +11,8 @@ namespace gpar {
 // the whitening then reads and overwrites in place (k_dist.hip).
 void whiten_kfu_any(gpar_ctx* c, const DevProblem& p, const GainsOut& gi, const double* v,
                            int64_t ldv, int64_t n, int64_t nch, const Theta& th, double* beta,
-                           int64_t ldb, double* send, double* hsum, bool d2_in_beta) {
+                           int64_t ldb, double* send, double* hsum, bool d2_in_beta, int span,
+                           const double* psi_pre) {
   const double s_o = th.sv_o * th.sv_o;
   const double* rec = gi.rec;
   const double* g = gi.g;
@@ -20,7 +21,10 @@ void whiten_kfu_any(gpar_ctx* c, const DevProblem& p, const GainsOut& gi, const 
   const double* d2 = cached_d2(c, p);
   if (d2 && v == p.v) {   // the fit's training inputs, distances cached (fit_impl)
     launch_whiten_kfu_d2(c->stream, p.tk, p.ok, rec, d2, p.mp, p.m, p.mp, n, kChunk, nch,
-                         1.0 / th.l_o, s_o, beta, ldb, send, p.mc, g, hsum, p.d2_is_r, tc, th.l_t);
+                         1.0 / th.l_o, s_o, beta, ldb, send, p.mc, g, hsum, p.d2_is_r, tc, th.l_t,
+                         span, psi_pre);
+  } else if (span > 1) {   // only the cached whitening walks spans (job_span)
+    throw Error(GPAR_ERR_STATE, "corr_span: the output's distance cache is gone");
   } else if (p.d > kFusedMaxD || gi.compact) {
     if (!d2_in_beta)   // else the caller's (timed) distance pass already wrote them
       launch_dist2(c->stream, p.ok, v, ldv, n, p.z, p.ldz, p.m, p.mp, (int)p.d, p.zc, beta, ldb);
@@ -36,6 +40,11 @@ void whiten_kfu_any(gpar_ctx* c, const DevProblem& p, const GainsOut& gi, const 
 }
 
 // Stage buffers under workspace names ending in sfx; idx: the stream lane (carry tags).
+// workspace tags of the span chain's carries: alpha's column over chunks, beta's columns over spans
+static std::string span_carry_tag(int idx, bool spans) {
+  return std::string(spans ? "fitcs" : "fitca") + (idx ? "_1" : "");
+}
+
 static StageBufs stage_bufs_named(gpar_ctx* c, int idx, const std::string& sfx, int64_t n,
                                   int64_t mpmax, double* send = nullptr, double* cin = nullptr) {
   const int64_t nch = (n + kChunk - 1) / kChunk;
@@ -50,8 +59,21 @@ static StageBufs stage_bufs_named(gpar_ctx* c, int idx, const std::string& sfx, 
   b.qv = ws<double>(c, "qv" + sfx, (size_t)nch * 4);
   return b;
 }
+// The buffers of a per-output Gram schedule (pipelined, split, lanes), whose jobs may whiten over
+// spans (corr_span): with the span transitions, alpha's chunk states and the scratch of the span
+// chain's two carries (stage_post_span), all taken here so that nothing is allocated once the
+// pipeline runs.
 StageBufs stage_bufs(gpar_ctx* c, int l, int64_t n, int64_t mpmax) {
-  return stage_bufs_named(c, l, l ? "_1" : "", n, mpmax);
+  const std::string sfx = l ? "_1" : "";
+  StageBufs b = stage_bufs_named(c, l, sfx, n, mpmax);
+  const int64_t nch = (n + kChunk - 1) / kChunk;
+  b.psi_pre = ws<double>(c, "psipre" + sfx, (size_t)nch * 9);
+  b.psi_span = ws<double>(c, "psispan" + sfx, (size_t)nch * 9);
+  b.acin = ws<double>(c, "acin" + sfx, (size_t)nch * 4);
+  reserve_carry(c, 3, nch, 1, 1, span_carry_tag(l, false));
+  for (int s = 2; s <= kMaxCorrSpan; s *= 2)
+    reserve_carry(c, 3, span_count(nch, s), mpmax + 1, 1, span_carry_tag(l, true));
+  return b;
 }
 
 // Outputs per grouped Gram launch set (0: per-output Grams).  Small problems only: one output's
@@ -123,7 +145,12 @@ void stage_whiten(gpar_ctx* c, const StageJob& j, const StageBufs& b) {
   // (16 + 4 doubles per step), beta written (m columns)
   const double in_cols = (cached || pass) ? (double)p.m : (double)p.d;
   Timed tm_(c, "whiten", 8.0 * (double)p.n * (in_cols + (double)p.m + 20.0));
-  whiten_kfu_any(c, p, j.gi, p.v, p.ldv, p.n, p.nch, *j.th, b.beta, p.mp, b.send, b.hsum, pass);
+  if (j.span > 1) {   // Psi_i of every chunk, each span's transition (the carry of beta's columns)
+    launch_span_psi(c->stream, p.sdim, j.gi.phi, p.nch, j.span, b.psi_pre, b.psi_span);
+    check_launch("span_psi");
+  }
+  whiten_kfu_any(c, p, j.gi, p.v, p.ldv, p.n, p.nch, *j.th, b.beta, p.mp, b.send, b.hsum, pass,
+                 j.span, b.psi_pre);
   check_launch("whiten_kfu");
 }
 
@@ -158,8 +185,31 @@ static void stage_post_tail(gpar_ctx* c, const StageJob& j, const StageBufs& b, 
   HIPCHECK(hipMemsetAsync(b.beta + (size_t)n * p.mp, 0, (size_t)16 * p.mp * sizeof(double), c->stream));
 }
 
+// The short chain of a job whitened over spans (j.span > 1; job_span: shared gains, no fix_beta).
+// alpha keeps its 256-step chunks: its end states (the gains pass's) take a one-column carry of
+// their own, and vec_fix_span fixes it in place chunk by chunk.  beta's columns are carried over
+// the spans with the span transitions; E_J, q_J per span.
+static void stage_post_span(gpar_ctx* c, const StageJob& j, const StageBufs& b) {
+  const DevProblem& p = *j.p;
+  const int64_t nsp = span_count(p.nch, j.span);
+  run_carry(c, p.sdim, j.gi.phi, 0, j.asend, b.acin, 0, p.nch, 1, 1, 1,
+            span_carry_tag(b.idx, false));
+  check_launch("carry alpha");
+  run_carry(c, p.sdim, b.psi_span, 0, b.send, b.cin, 0, nsp, p.mc, p.mp, 1,
+            span_carry_tag(b.idx, true));
+  check_launch("carry spans");
+  launch_vec_fix_span(c->stream, p.sdim, j.alpha, j.gi.g, b.acin, b.psi_pre, b.cin, p.mc, p.n,
+                      j.span, p.nch, j.a2part, b.hsum, p.mp, b.qv);
+  check_launch("vec_fix_span");
+  HIPCHECK(hipMemsetAsync(b.beta + (size_t)p.n * p.mp, 0, (size_t)16 * p.mp * sizeof(double), c->stream));
+}
+
 void stage_post(gpar_ctx* c, const StageJob& j, const StageBufs& b, bool fix_beta) {
   const DevProblem& p = *j.p;
+  if (j.span > 1) {
+    stage_post_span(c, j, b);
+    return;
+  }
   stage_post_head(c, j, b);
   run_carry(c, p.sdim, j.gi.phi, 0, b.send, b.cin, 0, p.nch, p.mc, p.mc, 1,
             b.idx ? "fitc_1" : "fitc");
@@ -196,7 +246,7 @@ void stage_gram(gpar_ctx* c, const StageJob& j, const StageBufs& b, bool fix_bet
   {
     Timed tm_(c, "gram", (double)p.n * (double)p.m * (double)(p.m + 1));   // flops of beta^T beta
     launch_gram(c->stream, p.sdim, plan, b.beta, p.mp, p.n, fix_beta ? nullptr : b.hsum, b.cin,
-                b.qv, p.mc, kChunk, j.alpha, part, rpart, j.G, j.ldg, j.r, side, c->ev_fork,
+                b.qv, p.mc, kChunk * j.span, j.alpha, part, rpart, j.G, j.ldg, j.r, side, c->ev_fork,
                 c->ev_join, st_w, ev_w, w_items);
   }
   check_launch("gram");
@@ -296,6 +346,17 @@ struct GramStage {
                             hipMemcpyDeviceToDevice, c->stream));
   }
 
+  // Chunks per span of output i's job (gpar_ctx::corr_span): above 1 only where the whitening is
+  // the cached whiten_kfu_d2x2 and the short chain is stage_post's per-output one with alpha from
+  // the shared gains pass -- not the grouped Gram (one batched carry per group), not fix_beta
+  // (q(u)), not the two-lane plan (the v2 Gram).  Decided after the job's last allocation (the
+  // span chain's buffers and carry scratch come with stage_bufs), so an out-of-memory eviction of
+  // the cache cannot fall between this and the whitening's launch.
+  int job_span(const DevProblem& p) const {
+    if (fix_beta || !sp.shared || sp.gram_group || sp.nlanes > 1) return 1;
+    return cached_job_span(c, p, sp.split, mpmax);
+  }
+
   // the stage job of output i; its gains (per output unless shared) run on c->stream
   const StageJob& job(int i, const StageBufs& b) {
     StageJob& j = jobs[i];
@@ -317,6 +378,7 @@ struct GramStage {
     j.a2part = o.a2part + (size_t)i * npart;
     j.ldg = mpmax;
     j.after = &after;
+    j.span = job_span(P[i]);
     return j;
   }
 };
@@ -333,7 +395,11 @@ static void gram_stage_split(GramStage& s) {
   gpar_ctx* c = s.c;
   SplitPipe pipe(c, s.n, s.mpmax);
   pipe.post_gram = c->post_gram == 1;
-  pipe.dg_rows_w = c->dg_rows_w == kDgRowsAuto ? 40 : c->dg_rows_w;
+  // auto: +30 where the round's cached outputs whiten over spans (less correction work beside
+  // OFF on the Gram CUs, a slightly longer whitening), else +40 (gpar_ctx::dg_rows_w)
+  bool spans = false;
+  for (const auto& p : s.P) spans = spans || s.job_span(p) > 1;
+  pipe.dg_rows_w = c->dg_rows_w == kDgRowsAuto ? (spans ? 30 : 40) : c->dg_rows_w;
   pipe.start();
   s.gplan.launch(c->s_w, 0, 1);
   s.gplan.launch(c->s_g2, 1, s.np - 1);

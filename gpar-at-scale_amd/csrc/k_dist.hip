@@ -19,6 +19,7 @@
 // are theta-independent, so gpar_host.cpp (attach_dist_cache) computes them once per fit for the
 // outputs it caches and every objective evaluation reads them.
 #include "device_common.hpp"
+#include "span.hpp"
 
 namespace gpar {
 
@@ -215,12 +216,21 @@ constexpr int kW2Occ = 2;   // workgroups per CU
 // CR: rec holds compact records {K, rs} (gains_phase3<D, true>); each step's transition A_k is
 // recomputed here from t (tau = (t_k - t_{k-1}) / l_t, as the gains pass computes it) while the
 // chunk's records are staged, which cuts the gains pass's HBM writes by more than half.
-template <int TK, int OK, bool RIN, bool CR>
+// SPAN (the "corr_span" plan, span.hpp): block j walks the `span` consecutive chunks j span ..
+// j span + span - 1 for its columns as one run of up to span x 256 rows (they are contiguous in
+// src and beta) and carries the filter states through instead of resetting them, so beta_loc,
+// send and hsum are local to the span.  Each chunk's records are restaged into the same LDS block
+// when the row loop crosses into it (one barrier pair per 256 steps; the d2 prefetch runs on
+// across the boundary); its fix-up rows are counted from the span start while they are staged,
+// g'_k = g_k Psi_i (psi: Psi_i per chunk, span_psi_kernel).  Requires L == kW2MaxL.  SPAN = false
+// is the one-chunk kernel.
+template <int TK, int OK, bool RIN, bool CR, bool SPAN>
 __global__ __launch_bounds__(256, kW2Occ) void whiten_kfu_d2x2(
     const double* __restrict__ rec, const double* src, int64_t lds, int64_t m, int64_t mp,
     int64_t n, int L, double inv_lo, double s_o, double* beta, int64_t ldb,
     double* __restrict__ send, int64_t mc, const double* __restrict__ g,
-    double* __restrict__ hsum, ExpNegConsts ek, const double* __restrict__ tt, double l_t) {
+    double* __restrict__ hsum, ExpNegConsts ek, const double* __restrict__ tt, double l_t,
+    int span, const double* __restrict__ psi) {
   constexpr int SD = Sde<TK>::d;
   constexpr int RS = Rec<SD>::size;
   // the chunk's step rows {A_k, K_k, rs_k, g_k}, 16 doubles each, read one double per lane and
@@ -234,29 +244,51 @@ __global__ __launch_bounds__(256, kW2Occ) void whiten_kfu_d2x2(
   const bool cola = c < mp;                                  // mp even: both or neither
   const bool v0 = c < m, v1 = c + 1 < m;
   const int64_t cc = cola ? c : 0;
-  const int64_t k0 = j * L;
-  const int64_t k1 = (k0 + L < n) ? k0 + L : n;
+  const int64_t LS = SPAN ? (int64_t)L * span : L;   // rows of a full block: the span, or the chunk
+  const int64_t k0 = j * LS;
+  const int64_t k1 = (k0 + LS < n) ? k0 + LS : n;
   const int nk = (int)(k1 - k0);
-  // the chunk's records and fix-up rows, once
-  if constexpr (CR) {
-    constexpr int CS = CRec<SD>::size;
-    for (int e = tid; e < nk; e += 256) {
-      const int64_t k = k0 + e;
-      double A[SD][SD];
-      sde_transition<SD>((k == 0) ? 1.0 : (tt[k] - tt[k - 1]) / l_t, A);
+  // the records and fix-up rows of the chunk that starts at the block's row c0 (0 when !SPAN), once
+  auto stage = [&](int c0) __attribute__((always_inline)) {
+    const int64_t kc = k0 + c0;
+    const int nc = (nk - c0 < L) ? nk - c0 : L;
+    if constexpr (CR) {
+      constexpr int CS = CRec<SD>::size;
+      for (int e = tid; e < nc; e += 256) {
+        const int64_t k = kc + e;
+        double A[SD][SD];
+        sde_transition<SD>((k == 0) ? 1.0 : (tt[k] - tt[k - 1]) / l_t, A);
 #pragma unroll
-      for (int i = 0; i < SD; ++i)
+        for (int i = 0; i < SD; ++i)
 #pragma unroll
-        for (int q = 0; q < SD; ++q) rg[e * 16 + i * SD + q] = A[i][q];
+          for (int q = 0; q < SD; ++q) rg[e * 16 + i * SD + q] = A[i][q];
 #pragma unroll
-      for (int i = 0; i <= SD; ++i) rg[e * 16 + RK + i] = rec[k * CS + i];
+        for (int i = 0; i <= SD; ++i) rg[e * 16 + RK + i] = rec[k * CS + i];
+      }
+    } else {
+      for (int e = tid; e < nc * RS; e += 256)
+        if (e % RS < RG) rg[e / RS * 16 + e % RS] = rec[kc * RS + e];
     }
-  } else {
-    for (int e = tid; e < nk * RS; e += 256)
-      if (e % RS < RG) rg[e / RS * 16 + e % RS] = rec[k0 * RS + e];
-  }
-  for (int e = tid; e < nk * kGStride; e += 256)
-    if (e % kGStride < SD) rg[e / kGStride * 16 + RG + e % kGStride] = g[k0 * kGStride + e];
+    if (SPAN && c0 > 0) {
+      const double* ps = psi + (kc / L) * SD * SD;
+      for (int e = tid; e < nc; e += 256) {
+        double gk[SD];
+#pragma unroll
+        for (int i = 0; i < SD; ++i) gk[i] = g[(kc + e) * kGStride + i];
+#pragma unroll
+        for (int q = 0; q < SD; ++q) {
+          double acc = 0.0;
+#pragma unroll
+          for (int i = 0; i < SD; ++i) acc = fma(gk[i], ps[i * SD + q], acc);
+          rg[e * 16 + RG + q] = acc;
+        }
+      }
+    } else {
+      for (int e = tid; e < nc * kGStride; e += 256)
+        if (e % kGStride < SD) rg[e / kGStride * 16 + RG + e % kGStride] = g[kc * kGStride + e];
+    }
+  };
+  stage(0);
   double ma[SD], mb[SD], ha[SD], hb[SD];
 #pragma unroll
   for (int i = 0; i < SD; ++i) ma[i] = mb[i] = ha[i] = hb[i] = 0.0;
@@ -278,6 +310,13 @@ __global__ __launch_bounds__(256, kW2Occ) void whiten_kfu_d2x2(
   if (nk > 0) prefetch(0);
   __syncthreads();
   for (int r0 = 0; r0 < nk; r0 += kW2T) {
+    if constexpr (SPAN) {
+      if (r0 > 0 && (r0 & (kW2MaxL - 1)) == 0) {   // into the span's next chunk
+        __syncthreads();                            // every wave is done with the last chunk's rows
+        stage(r0);
+        __syncthreads();
+      }
+    }
     double2 x[kW2T];
 #pragma unroll
     for (int r = 0; r < kW2T; ++r) x[r] = px[r];
@@ -305,7 +344,7 @@ __global__ __launch_bounds__(256, kW2Occ) void whiten_kfu_d2x2(
       x[r].y = v1 ? kb : 0.0;
     }
     auto step = [&](int r) __attribute__((always_inline)) {
-      const double row = rg[(r0 + r) * 16 + (tid & 15)];
+      const double row = rg[(SPAN ? (r0 + r) & (kW2MaxL - 1) : r0 + r) * 16 + (tid & 15)];
       double pa[SD], pb[SD];
       static_for<SD>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -415,25 +454,36 @@ template <int TK, int OK, bool RIN>
 static void launch_wd2_k(hipStream_t st, dim3 grid, const double* rec, const double* src,
                          int64_t lds, int64_t m, int64_t mp, int64_t n, int L, double inv_lo,
                          double s_o, double* beta, int64_t ldb, double* send, int64_t mc,
-                         const double* g, double* hsum, const double* tt, double l_t) {
+                         const double* g, double* hsum, const double* tt, double l_t, int span,
+                         const double* psi) {
   if (L > kW2MaxL || (lds & 1) || (ldb & 1))
     throw std::runtime_error("whiten_kfu_d2x2: chunk length > 256 or odd leading dimension");
-  if (tt)
-    whiten_kfu_d2x2<TK, OK, RIN, true><<<grid, 256, 0, st>>>(rec, src, lds, m, mp, n, L, inv_lo,
-                                                             s_o, beta, ldb, send, mc, g, hsum,
-                                                             exp_neg_consts(), tt, l_t);
-  else
-    whiten_kfu_d2x2<TK, OK, RIN, false><<<grid, 256, 0, st>>>(rec, src, lds, m, mp, n, L, inv_lo,
-                                                              s_o, beta, ldb, send, mc, g, hsum,
-                                                              exp_neg_consts(), nullptr, 0.0);
+#define WD2_LAUNCH(CRV, SPV, TT, LT)                                                            \
+  whiten_kfu_d2x2<TK, OK, RIN, CRV, SPV><<<grid, 256, 0, st>>>(                                 \
+      rec, src, lds, m, mp, n, L, inv_lo, s_o, beta, ldb, send, mc, g, hsum, exp_neg_consts(),  \
+      TT, LT, span, psi)
+  if (span > 1) {
+    if (!psi || !corr_span_valid(span) || L != kW2MaxL)
+      throw std::runtime_error("whiten_kfu_d2x2: span without its transitions, not 2 / 4 / 8, or chunks not of 256");
+    if (tt)
+      WD2_LAUNCH(true, true, tt, l_t);
+    else
+      WD2_LAUNCH(false, true, nullptr, 0.0);
+  } else if (tt) {
+    WD2_LAUNCH(true, false, tt, l_t);
+  } else {
+    WD2_LAUNCH(false, false, nullptr, 0.0);
+  }
+#undef WD2_LAUNCH
 }
 
 template <int TK>
 static void launch_wd2_t(hipStream_t st, int ok, bool rin, dim3 grid, const double* rec,
                          const double* src, int64_t lds, int64_t m, int64_t mp, int64_t n, int L,
                          double inv_lo, double s_o, double* beta, int64_t ldb, double* send,
-                         int64_t mc, const double* g, double* hsum, const double* tt, double l_t) {
-#define WD2_ARGS st, grid, rec, src, lds, m, mp, n, L, inv_lo, s_o, beta, ldb, send, mc, g, hsum, tt, l_t
+                         int64_t mc, const double* g, double* hsum, const double* tt, double l_t,
+                         int span, const double* psi) {
+#define WD2_ARGS st, grid, rec, src, lds, m, mp, n, L, inv_lo, s_o, beta, ldb, send, mc, g, hsum, tt, l_t, span, psi
   if (rin) {
     switch (ok) {
       case KM12: launch_wd2_k<TK, KM12, true>(WD2_ARGS); break;
@@ -457,9 +507,10 @@ void launch_whiten_kfu_d2(hipStream_t st, int time_kind, int out_kind, const dou
                           const double* src, int64_t lds, int64_t m, int64_t mp, int64_t n, int L,
                           int64_t nch, double inv_lo, double s_o, double* beta, int64_t ldb,
                           double* send, int64_t mc, const double* g, double* hsum, bool src_is_r,
-                          const double* t_compact, double l_t) {
-  dim3 grid((unsigned)nch, (unsigned)((mp + 511) / 512));
-#define WD2T_ARGS st, out_kind, src_is_r, grid, rec, src, lds, m, mp, n, L, inv_lo, s_o, beta, ldb, send, mc, g, hsum, t_compact, l_t
+                          const double* t_compact, double l_t, int span, const double* psi_pre) {
+  // span > 1: one workgroup per span of `span` chunks (nch counts chunks either way)
+  dim3 grid((unsigned)span_count(nch, span > 1 ? span : 1), (unsigned)((mp + 511) / 512));
+#define WD2T_ARGS st, out_kind, src_is_r, grid, rec, src, lds, m, mp, n, L, inv_lo, s_o, beta, ldb, send, mc, g, hsum, t_compact, l_t, span, psi_pre
   switch (time_kind) {
     case KM12: launch_wd2_t<KM12>(WD2T_ARGS); break;
     case KM32: launch_wd2_t<KM32>(WD2T_ARGS); break;

@@ -173,7 +173,7 @@ void launch_whiten_kfu_d2(hipStream_t st, int time_kind, int out_kind, const dou
                           int64_t nch, double inv_lo, double s_o, double* beta, int64_t ldb,
                           double* send, int64_t mc, const double* g, double* hsum,
                           bool src_is_r = false, const double* t_compact = nullptr,
-                          double l_t = 0.0);
+                          double l_t = 0.0, int span = 1, const double* psi_pre = nullptr);
 void launch_whiten_vec(hipStream_t st, int sdim, const double* rec, int64_t recstride,
                        const double* y, int64_t ldy, int64_t n, int L, int64_t nch, int nchains,
                        double* alpha, int64_t lda, double* send, int64_t sendstride, int64_t mc,
@@ -220,6 +220,13 @@ void launch_vec_fix(hipStream_t st, int sdim, double* alpha, int64_t lda, const 
                     int64_t gstride, const double* cin, int64_t sstride, int64_t mc,
                     int64_t col, int64_t n, int L, int nchains, double* part,
                     double* hsum = nullptr, int64_t ncols = 0, double* qout = nullptr);
+// k_span.hip: the corr_span plan's span transitions and its vec_fix (span.hpp)
+void launch_span_psi(hipStream_t st, int sdim, const double* phi, int64_t nch, int span,
+                     double* pre, double* tot);
+void launch_vec_fix_span(hipStream_t st, int sdim, double* alpha, const double* g,
+                         const double* acin, const double* pre, const double* cin, int64_t mc,
+                         int64_t n, int span, int64_t nch, double* part, double* hsum,
+                         int64_t ncols, double* qout);
 void launch_chain_lml(hipStream_t st, const double* logs, int64_t nch, const double* a2part,
                       int64_t npart, int64_t n, int nchains, double* lml);
 

@@ -32,6 +32,7 @@ EXPORTED = (
     "gpar_nm_create", "gpar_nm_destroy", "gpar_nm_ask", "gpar_nm_tell", "gpar_nm_result",
     "gpar_select_pseudo_inputs",
     "gpar_predict_samples", "gpar_posterior_predict_samples",
+    "gpar_corr_span_plan", "gpar_corr_span_psi",
 )
 
 
@@ -157,8 +158,12 @@ def load(path: str | None = None):
             "gpar_nm_tell": (i32, [vp, C.c_double]),
             "gpar_nm_result": (i32, [vp, dp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32)]),
         })
+        sig.update({
+            "gpar_corr_span_plan": (i32, [i32, i32, i32, i64, i64, C.POINTER(i32), C.POINTER(i64)]),
+            "gpar_corr_span_psi": (i32, [i32, i64, i32, dp, dp, dp]),
+        })
         later = ("gpar_debug_counter", "gpar_predict_mean", "gpar_posterior_predict_mean",
-                 "gpar_posterior_prepare_mean")
+                 "gpar_posterior_prepare_mean", "gpar_corr_span_plan", "gpar_corr_span_psi")
         for name, (res, args) in sig.items():
             if name in later and not hasattr(lib, name):
                 continue   # older builds (library A/B runs, tools/lib_bitcheck.py) lack these
@@ -299,9 +304,9 @@ class Context:
     def set_schedule(self, knob, value):
         """A schedule knob (gpar_ctx_set_schedule: overlap, overlap_group, qu_batch, dense_early,
         post_gram, compact_rec, predict_lanes, serialize, predict_fused, dg_rows_w, gram_group,
-        scaled_gram, fit_chunks, device_nm, chain_mean_first; the header lists their values);
+        scaled_gram, fit_chunks, device_nm, chain_mean_first, corr_span; the header lists their values);
         results are bit-identical with any setting except the plan knobs predict_fused, dg_rows_w,
-        gram_group and scaled_gram (last bits), device_nm (the device's exp() in the chains fit's
+        gram_group, scaled_gram and corr_span (last bits), device_nm (the device's exp() in the chains fit's
         parameters) and chain_mean_first (a chained call's means come from the mean-only path)."""
         self.check(load().gpar_ctx_set_schedule(self.h, knob.encode(), int(value)))
 

@@ -122,6 +122,17 @@ int32_t gpar_ctx_kernel_work(gpar_ctx* ctx, const char* name, double* work);
  * one-lane-per-chunk / the four-lanes-per-chunk kernel (the size rule, or the environment variable
  * GPAR_GAINS_P1_LANES=1 / 4, which forces one of them for tests).  -1 for an unknown name. */
 int64_t gpar_debug_counter(const char* name);
+/* The "corr_span" plan's host arithmetic (no device work; tests, debug only): the span a fit call
+ * of `outputs` outputs, n steps and padded width mp takes under the knob value `knob` (-1 = auto)
+ * with the CU split on or off, and the spans that cover its ceil(n / 256) chunks. */
+int32_t gpar_corr_span_plan(int32_t knob, int32_t split, int32_t outputs, int64_t n, int64_t mp,
+                            int32_t* span, int64_t* nspans);
+/* ... and the chunk transitions composed over spans as the device composes them: phi holds nch
+ * row-major sdim x sdim closed-loop chunk transitions; pre[j] = Psi_i = Phi_{j-1} ... Phi_{j0} for
+ * chunk j = j0 + i of the span starting at chunk j0 (Psi_0 = I), tot[J] = the transition over span
+ * J's chunks (ceil(nch / span) matrices). */
+int32_t gpar_corr_span_psi(int32_t sdim, int64_t nch, int32_t span, const double* phi, double* pre,
+                           double* tot);
 /* Concurrency of batched calls (gpar_dtc_objective / gpar_fit with nprob > 1): lanes = 2
  * alternates the outputs' whitening + Gram between two HIP streams with separate workspaces so
  * one output's whitening overlaps another's Gram (~1 % faster at N = 1e6, M = 512, two beta
@@ -175,7 +186,7 @@ int32_t gpar_ctx_set_predict_fused(gpar_ctx* ctx, int32_t on);
  *   "predict_fused" as gpar_ctx_set_predict_fused (changes the summation order: last bits)
  *   "dg_rows_w"     percent more rows per diagonal-block time split on the whitening CUs of a
  *                   split Gram, fewer on the Gram CUs; -100 (default) = auto: 40 in the
- *                   round-by-round fit, 20 in the round overlap (changes G's summation grouping:
+ *                   round-by-round fit (30 where corr_span > 1 applies), 20 in the round overlap (changes G's summation grouping:
  *                   last bits, like predict_fused)
  *   "scaled_gram"   1 (default): a batched fit keeps each output's first Gram of the call (G, r and
  *                   the alpha^2 / log S sums, 8 Mp^2 bytes per output) and serves the evaluations
@@ -186,6 +197,17 @@ int32_t gpar_ctx_set_predict_fused(gpar_ctx* ctx, int32_t on);
  *                   evaluation computes its own.  A plan like dg_rows_w: bit-identical to its
  *                   serialized twin, last bits against 0.  gpar_dtc_objective*, q(u) and the
  *                   predictions never rescale (the Gram gpar_fit_predict keeps for q(u) may be one)
+ *   "corr_span"     chunks per span of the batched fit's cached whitening, 1 / 2 / 4 / 8: the
+ *                   filter state of an output whitened from the fit's distance cache is reset every
+ *                   S x 256 steps instead of every 256, so the Gram's chunk correction, the carry
+ *                   of beta's columns and the correction's per-chunk inputs (E_j, C_j, q_j) run
+ *                   over ceil(nch / S) spans.  1 = the one-chunk code path; -1 (default) = auto:
+ *                   2 in fit calls of more than 16 outputs that take the CU split with
+ *                   N Mp^2 >= 1e11 (the round-by-round split fit), 1 elsewhere.  Applies to gpar_fit / gpar_fit_predict* rounds that run per-output
+ *                   Grams on shared gains (the pipelined and CU-split schedules, the round overlap
+ *                   on the split); the uncached whitening, the grouped Gram, gpar_dtc_objective*,
+ *                   q(u), the predictions and the temporal chains keep 1.  A plan like dg_rows_w:
+ *                   bit-identical to its serialized twin, last bits against 1
  *   "gram_group"    outputs per grouped Gram of an unsplit batched fit: the group's outputs whiten
  *                   over two streams into buffers of their own and one set of Gram launches covers
  *                   them all (grid y = output), each with 1/g of the time splits; -1 (default) =
