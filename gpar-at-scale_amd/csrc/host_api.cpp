@@ -271,6 +271,8 @@ int64_t gpar_debug_counter(const char* name) {
   if (std::strcmp(name, "gains_general") == 0) return g_gains_general_launches.load();
   if (std::strcmp(name, "gains_p1_lane1") == 0) return g_gains_p1_lane1_launches.load();
   if (std::strcmp(name, "gains_p1_lane4") == 0) return g_gains_p1_lane4_launches.load();
+  if (std::strcmp(name, "quantile_reg") == 0) return g_quantile_reg_launches.load();
+  if (std::strcmp(name, "quantile_lds") == 0) return g_quantile_lds_launches.load();
   return -1;
 }
 

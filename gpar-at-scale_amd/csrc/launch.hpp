@@ -380,6 +380,21 @@ void launch_path_stats(hipStream_t st, const double* fx, int64_t ldfx, const dou
                        const int64_t* pos, int64_t nstar, double* mean, double* std);
 void launch_path_transpose(hipStream_t st, const double* F, int64_t n, int S, double* out);
 
+// k_quantile.hip (quantiles over the sample axis; layouts and the two paths in the file header)
+constexpr int kQuantMaxS = 4096;       // longest list (the LDS path's)
+constexpr int kQuantRegMax = 128;      // longest list the register path takes (no scratch: DESIGN 4.9)
+constexpr int kQuantMaxQ = 16;         // quantiles per launch (passed by value)
+constexpr int kQuantLdsDoubles = 4096; // LDS doubles per workgroup of the LDS path (32 KB)
+constexpr int kQuantLdsMaxG = 16;      // most lists per workgroup
+// launches by path (gpar_debug_counter "quantile_reg" / "quantile_lds"; GPAR_QUANTILE_PATH=reg /
+// lds forces one where it can serve the size)
+extern std::atomic<int64_t> g_quantile_reg_launches, g_quantile_lds_launches;
+// out[j * ldo_q + i * ldo_r + c * ldo_c] = the quantile (lo[j], g[j]) of entry (i, c)'s S samples
+// F[s * ld_s + i * ld_r + c * ld_c]; nq <= kQuantMaxQ, S <= kQuantMaxS, lo / g host arrays
+void launch_quantiles(hipStream_t st, const double* F, int S, int64_t n, int64_t p, int64_t ld_s,
+                      int64_t ld_r, int64_t ld_c, int nq, const int* lo, const double* g,
+                      double* out, int64_t ldo_q, int64_t ldo_r, int64_t ldo_c);
+
 // k_exact.hip
 void launch_exact_cov(hipStream_t st, const double* x, int64_t ldx, int64_t n, const double* x2,
                       int64_t ldx2, int64_t n2, int dx, int tk, int ok, double inv_lt, double s_t,

@@ -33,6 +33,7 @@ EXPORTED = (
     "gpar_select_pseudo_inputs",
     "gpar_predict_samples", "gpar_posterior_predict_samples",
     "gpar_corr_span_plan", "gpar_corr_span_psi",
+    "gpar_sample_quantiles",
 )
 
 
@@ -162,8 +163,13 @@ def load(path: str | None = None):
             "gpar_corr_span_plan": (i32, [i32, i32, i32, i64, i64, C.POINTER(i32), C.POINTER(i64)]),
             "gpar_corr_span_psi": (i32, [i32, i64, i32, dp, dp, dp]),
         })
+        sig.update({
+            "gpar_sample_quantiles": (i32, [vp, i32, i64, i64, dp, i64, i64, i64, i32, dp, i32, dp,
+                                            i64, i64, i64]),
+        })
         later = ("gpar_debug_counter", "gpar_predict_mean", "gpar_posterior_predict_mean",
-                 "gpar_posterior_prepare_mean", "gpar_corr_span_plan", "gpar_corr_span_psi")
+                 "gpar_posterior_prepare_mean", "gpar_corr_span_plan", "gpar_corr_span_psi",
+                 "gpar_sample_quantiles")
         for name, (res, args) in sig.items():
             if name in later and not hasattr(lib, name):
                 continue   # older builds (library A/B runs, tools/lib_bitcheck.py) lack these
@@ -204,7 +210,9 @@ def _torch_runtime_first():
 def debug_counter(name):
     """A process-wide diagnostic counter of the library (gpar_debug_counter): "gains_fast" /
     "gains_general" = phase-3 gains launches by kernel path; "gains_p1_lane1" / "gains_p1_lane4" =
-    phase-1 gains launches by lanes per chunk (GPAR_GAINS_P1_LANES=1 / 4 forces one)."""
+    phase-1 gains launches by lanes per chunk (GPAR_GAINS_P1_LANES=1 / 4 forces one);
+    "quantile_reg" / "quantile_lds" = sample_quantiles' launches by path (GPAR_QUANTILE_PATH=reg /
+    lds forces one)."""
     return int(load().gpar_debug_counter(name.encode()))
 
 

@@ -637,6 +637,86 @@ def predict_samples_scaled(input_locations, pseudo_input_locations, time_loc, ou
                          shared_inputs, sample_inputs, samples, seed, out, device)
 
 
+def sample_quantiles(F, q, out=None, device=0):
+    """Quantiles over the sample axis of joint samples (gpar_sample_quantiles): the credible bands
+    of a sample chain, computed in place on the device.  F: S x N* or S x N* x P float64 samples, a
+    numpy array (host memory) or a torch device tensor, any positive strides -- the chain tensor
+    sample_chain returns, a column chain[:, :, c] or a row block of it are read where they are.
+    q: a sequence of levels in [0, 1], any order.  Returns the len(q) x N* (x P) quantiles by
+    numpy's default method ("linear"), bit-identical whatever the strides or the memory kind; an
+    entry with a NaN sample gives NaN.  out: an array / tensor of that shape (any positive strides)
+    to write into.  S <= 4096."""
+    dev = _is_torch(F)
+    if not dev and not isinstance(F, np.ndarray):
+        raise _arg_error("F must be a numpy array or a torch device tensor")
+    if dev:
+        import torch
+        f64 = F.dtype == torch.float64
+    else:
+        f64 = F.dtype == np.float64
+    if not f64:
+        raise _arg_error("F must be float64")
+    if len(F.shape) not in (2, 3):
+        raise _arg_error("F must be S x N* or S x N* x P")
+    shape = tuple(int(x) for x in F.shape)
+    if min(shape) < 1:
+        raise _arg_error("F must not be empty")
+    try:
+        qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64).ravel())
+    except (TypeError, ValueError):
+        raise _arg_error("q must be a sequence of numbers in [0, 1]") from None
+    if qa.size < 1:
+        raise _arg_error("q must hold at least one level")
+    if not bool(np.all((qa >= 0.0) & (qa <= 1.0))):   # a NaN fails both comparisons
+        raise _arg_error("every q must be in [0, 1]")
+    nq = int(qa.size)
+    oshape = (nq,) + shape[1:]
+
+    def strides(a):
+        # in doubles; a dimension of one element never steps, whatever stride it carries
+        if dev:
+            ld = [int(x) for x in a.stride()]
+        elif any(x % 8 for x in a.strides):
+            raise _arg_error("strides must be multiples of 8 bytes")
+        else:
+            ld = [x // 8 for x in a.strides]
+        return tuple(1 if m == 1 else x for x, m in zip(ld, a.shape))
+
+    if out is not None:
+        same_kind = _is_torch(out) if dev else isinstance(out, np.ndarray)
+        if not same_kind or tuple(out.shape) != oshape or out.dtype != F.dtype:
+            raise _arg_error(f"out must be a float64 {'tensor' if dev else 'array'} of shape {oshape}")
+        if dev and out.device != F.device:
+            raise _arg_error("out must live on F's device")
+        if not dev and not out.flags.writeable:
+            raise _arg_error("out must be writable")
+    lf = strides(F)
+    lo = strides(out) if out is not None else None
+    if min(lf) < 1 or (lo is not None and min(lo) < 1):
+        raise _arg_error("strides must be positive")
+    if dev and not F.is_cuda:
+        raise _arg_error("torch tensors must be device tensors (host data: numpy arrays)")
+    S, n = shape[0], shape[1]
+    p = shape[2] if len(shape) == 3 else 1
+    ctx, lib = context(device), _lib.load()
+    if out is None:
+        if dev:
+            import torch
+            out = torch.empty(oshape, dtype=torch.float64, device=F.device)
+        else:
+            out = np.empty(oshape)
+        lo = strides(out)
+    lf3 = lf if len(shape) == 3 else lf + (1,)
+    lo3 = lo if len(shape) == 3 else lo + (1,)
+    fp = F.data_ptr() if dev else F.ctypes.data
+    op = out.data_ptr() if dev else out.ctypes.data
+    mem = _lib.GPAR_MEM_DEVICE if dev else _lib.GPAR_MEM_HOST
+    with _after_torch(ctx, dev):
+        ctx.check(lib.gpar_sample_quantiles(ctx.h, S, n, p, fp, lf3[0], lf3[1], lf3[2], nq, _ptr(qa),
+                                            mem, op, lo3[0], lo3[1], lo3[2]))
+    return out
+
+
 class Posterior:
     """gpar_fit_posterior's result: the fitted theta of every output and its q(u), kept on the
     device, so that predictions whose inference inputs arrive later (the chained sweep of
@@ -740,7 +820,8 @@ class Posterior:
         (device).  Allocates the S x N* x P chain tensor and sweeps the outputs in order: output i
         reads columns [:i] of every sample's slab in place, draws with seed + i (fit_predict_batch's
         convention) and writes column i.  Returns (samples S x N* x P, means, stds), means / stds
-        lists of the per-output sample mean and Bessel std.  One rank only."""
+        lists of the per-output sample mean and Bessel std.  One rank only.
+        sample_chain_quantiles adds the chain's credible bands."""
         P = len(self._problems)
         S = int(samples)
         dev = self._problems[0].mem == _lib.GPAR_MEM_DEVICE
@@ -766,6 +847,15 @@ class Posterior:
             means.append(m)
             stds.append(s)
         return chain, means, stds
+
+    def sample_chain_quantiles(self, t_star, given_inputs, samples, quantiles, seed=0):
+        """sample_chain with the chain's credible bands: returns (samples, means, stds, bands),
+        the first three exactly sample_chain's for the same arguments, bands the len(quantiles) x
+        N* x P quantiles of the chain over its samples at the levels `quantiles` (a sequence in
+        [0, 1]) -- one sample_quantiles call over the whole chain tensor after the sweep, which
+        reads it in place."""
+        chain, means, stds = self.sample_chain(t_star, given_inputs, samples, seed=seed)
+        return chain, means, stds, sample_quantiles(chain, quantiles, device=self.device)
 
     def prepare(self, i, t_star):
         """Queue output i's inference-input-independent prediction work for device test times

@@ -120,7 +120,8 @@ int32_t gpar_ctx_kernel_work(gpar_ctx* ctx, const char* name, double* work);
  * gains' phase-3 launches that took the LDS-DMA fast kernel / the general kernels since the library
  * was loaded; "gains_p1_lane1" / "gains_p1_lane4" = the gains' phase-1 launches that took the
  * one-lane-per-chunk / the four-lanes-per-chunk kernel (the size rule, or the environment variable
- * GPAR_GAINS_P1_LANES=1 / 4, which forces one of them for tests).  -1 for an unknown name. */
+ * GPAR_GAINS_P1_LANES=1 / 4, which forces one of them for tests); "quantile_reg" / "quantile_lds" =
+ * gpar_sample_quantiles' launches on the register / the LDS path.  -1 for an unknown name. */
 int64_t gpar_debug_counter(const char* name);
 /* The "corr_span" plan's host arithmetic (no device work; tests, debug only): the span a fit call
  * of `outputs` outputs, n steps and padded width mp takes under the knob value `knob` (-1 = auto)
@@ -501,6 +502,33 @@ int32_t gpar_posterior_predict_samples(gpar_ctx* ctx, const gpar_posterior* post
                                        int32_t samples, uint64_t seed, double* f_out,
                                        int64_t ldf_s, int64_t ldf_r, double* mean, double* std);
 int32_t gpar_posterior_destroy(gpar_posterior* post);
+
+/* ---------------------------------------------------------------- quantiles of samples
+ * Quantiles over the sample axis of a samples x n x p tensor, element (s, i, c) at
+ * f[s*ld_s + i*ld_r + c*ld_c] (strides in doubles, all positive: the chain tensor of
+ * gpar_predict_samples, or any view of it -- a column, a row block), computed in place:
+ * out[j*ldo_q + i*ldo_r + c*ldo_c] = quantile q[j] of entry (i, c)'s samples by numpy's default
+ * method ("linear", Hyndman-Fan type 7).  With x the ascending sort of the entry's samples,
+ * h = q (samples - 1), lo = floor(h), g = h - lo, a = x[lo], b = x[min(lo + 1, samples - 1)]: the
+ * result is a when g = 0 or a = b, else a + (b - a) g for g < 1/2 and b - (b - a)(1 - g) for
+ * g >= 1/2, each operation rounded once (no FMA).  An entry with a NaN sample gives NaN for every
+ * q; +-inf sort as values.  q [nq]: host, any order, repeats allowed.  f and out in `mem`: device
+ * tensors are read in place with no workspace (the call honours gpar_ctx_set_input_stream and
+ * returns when the results are written); host tensors are staged in blocks of at most 256 MB.
+ * An entry's result depends on its samples and q alone -- not on the strides, the memory kind or
+ * its neighbours.  samples <= 128: one lane sorts an entry in registers (Batcher's odd-even
+ * mergesort); up to 4096: a workgroup sorts in LDS (gpar_debug_counter "quantile_reg" /
+ * "quantile_lds" count the launches by path; the environment variable GPAR_QUANTILE_PATH=reg / lds
+ * forces one, for tests, where it can serve the size).  GPAR_ERR_ARG, before any launch, for
+ * samples, n, p or nq < 1, a q outside [0, 1] or NaN, a NULL pointer, a non-positive stride, strides
+ * under which two elements of f or of out share an address (taken in order of their strides, each
+ * dimension must step past the extent of the narrower ones), an unknown mem;
+ * GPAR_ERR_UNSUPPORTED for samples > 4096.  Event-timing family "quantile" (gpar_ctx_kernel_work:
+ * HBM bytes, 8 samples n p per launch; one launch per 16 quantiles). */
+int32_t gpar_sample_quantiles(gpar_ctx* ctx, int32_t samples, int64_t n, int64_t p,
+                              const double* f, int64_t ld_s, int64_t ld_r, int64_t ld_c,
+                              int32_t nq, const double* q, int32_t mem, double* out,
+                              int64_t ldo_q, int64_t ldo_r, int64_t ldo_c);
 
 /* ---------------------------------------------------------------- temporal-only (LGSSM) chains
  * `nchains` independent chains sharing the time grid t [n] (ascending); chain c's

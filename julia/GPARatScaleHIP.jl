@@ -23,6 +23,10 @@ and joint samples of an output whose inference inputs differ per sample (GPAR's 
 
   get_gpar_scaled_prediction_samples -> (F, means, stds)
 
+and the quantiles of such samples over the sample axis (credible bands):
+
+  sample_quantiles                   -> bands
+
 with every number computed by the gfx950 kernels behind include/gpar_hip.h.  A caller switches
 `using GPARatScale` to `using GPARatScale, GPARatScaleHIP` and qualifies these five names (or
 imports them from GPARatScaleHIP).  The reference's helpers (to_ColVecs, unpack_gpar,
@@ -47,7 +51,7 @@ using GPARatScale: to_ColVecs, unpack_gpar, unpack_gp, parse_initial_gpar_params
 
 export compute_gpar_dtc_objective, get_optim_scaled_gpar_params, compute_q_u,
        get_gpar_scaled_predictions, get_sde_predictions, get_gpar_scaled_predictions_batch,
-       select_pseudo_inputs, get_gpar_scaled_prediction_samples
+       select_pseudo_inputs, get_gpar_scaled_prediction_samples, sample_quantiles
 
 const libgpar = get(ENV, "GPAR_HIP_LIB", "libgparhip.so")
 
@@ -384,6 +388,42 @@ function get_gpar_scaled_prediction_samples(input_locations, pseudo_input_locati
                        stds))
     end
     return F, means, stds
+end
+
+# ------------------------------------------------------------------ quantiles of samples
+"""
+    sample_quantiles(F, q)
+
+Quantiles over the sample axis of joint samples (gpar_sample_quantiles): `F` an N* x S matrix as
+get_gpar_scaled_prediction_samples returns it (column s = sample s), or an N* x P x S array of P
+outputs' samples; any strided Float64 array of that shape is read where it is, its strides passed
+on.  `q`: levels in [0, 1], any order.  Returns the N* x length(q) (N* x P x length(q)) quantiles
+by the "linear" method (Statistics.quantile's default, Hyndman-Fan type 7); an entry with a NaN
+sample gives NaN.  At most 4096 samples.
+"""
+function sample_quantiles(F::StridedArray{Float64}, q)
+    ndims(F) == 2 || ndims(F) == 3 ||
+        throw(DomainError(ndims(F), "F must be N* x S or N* x P x S"))
+    qs = Vector{Float64}(collect(q))
+    isempty(qs) && throw(DomainError(0, "q must hold at least one level"))
+    all(x -> 0.0 <= x <= 1.0, qs) || throw(DomainError(qs, "every q must be in [0, 1]"))
+    ns, P, S = size(F, 1), ndims(F) == 3 ? size(F, 2) : 1, size(F, ndims(F))
+    min(ns, P, S) >= 1 || throw(DomainError(size(F), "F must not be empty"))
+    ldr = Int64(stride(F, 1))
+    ldc = ndims(F) == 3 ? Int64(stride(F, 2)) : Int64(1)
+    lds = Int64(stride(F, ndims(F)))
+    nq = length(qs)
+    out = ndims(F) == 3 ? zeros(ns, P, nq) : zeros(ns, nq)
+    c = ctx()
+    GC.@preserve F qs out begin
+        check(c, ccall((:gpar_sample_quantiles, libgpar), Int32,
+                       (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64, Int32,
+                        Ptr{Float64}, Int32, Ptr{Float64}, Int64, Int64, Int64),
+                       c.h, Int32(S), Int64(ns), Int64(P), pointer(F), lds, ldr, ldc, Int32(nq),
+                       pointer(qs), GPAR_MEM_HOST, pointer(out), Int64(ns * P), Int64(1),
+                       Int64(ns)))
+    end
+    return out
 end
 
 # ------------------------------------------------------------------ the GPAR per-output driver loop
