@@ -258,6 +258,9 @@ inline void d2h(gpar_ctx* c, T* dst, const T* src, size_t count) {
 inline void sync(gpar_ctx* c) { HIPCHECK(hipStreamSynchronize(c->stream)); }
 void h2d_rows(gpar_ctx* c, double* dst, const double* src, int64_t ld, int64_t width,
                      int64_t rows);
+// no two elements of a tensor of these sizes and (positive) strides share an address
+// (host_quantile.cpp)
+bool strides_disjoint(const int64_t (&size)[3], const int64_t (&ld)[3]);
 
 // Route the launches of a scope to another stream (all helpers launch on c->stream).
 struct OnStream {

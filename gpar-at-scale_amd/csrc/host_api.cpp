@@ -273,6 +273,8 @@ int64_t gpar_debug_counter(const char* name) {
   if (std::strcmp(name, "gains_p1_lane4") == 0) return g_gains_p1_lane4_launches.load();
   if (std::strcmp(name, "quantile_reg") == 0) return g_quantile_reg_launches.load();
   if (std::strcmp(name, "quantile_lds") == 0) return g_quantile_lds_launches.load();
+  if (std::strcmp(name, "score_reg") == 0) return g_score_reg_launches.load();
+  if (std::strcmp(name, "score_lds") == 0) return g_score_lds_launches.load();
   return -1;
 }
 

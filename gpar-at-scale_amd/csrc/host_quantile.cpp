@@ -8,14 +8,10 @@
 
 using namespace gpar;
 
-namespace {
-
-constexpr int64_t kQuantStageBytes = (int64_t)256 << 20;   // most staged bytes of F per host block
-
 // No two elements of a tensor of the given sizes and (positive) strides share an address: taken
 // in order of their strides, every dimension of more than one element steps past the extent of
 // the narrower ones (the check gpar_predict_samples makes of ld_s against (n_star - 1) ld_r + d)
-bool strides_disjoint(const int64_t (&size)[3], const int64_t (&ld)[3]) {
+bool gpar::strides_disjoint(const int64_t (&size)[3], const int64_t (&ld)[3]) {
   int ord[3] = {0, 1, 2};
   std::sort(ord, ord + 3, [&](int a, int b) { return ld[a] < ld[b]; });
   __int128 extent = 1;   // 1 + the largest offset over the dimensions seen so far
@@ -26,6 +22,10 @@ bool strides_disjoint(const int64_t (&size)[3], const int64_t (&ld)[3]) {
   }
   return extent <= ((__int128)1 << 60);
 }
+
+namespace {
+
+constexpr int64_t kQuantStageBytes = (int64_t)256 << 20;   // most staged bytes of F per host block
 
 // the launches of one tensor already on the device: kQuantMaxQ quantiles per launch
 void run_quantiles(gpar_ctx* c, const double* f, int S, int64_t n, int64_t p, int64_t ld_s,

@@ -395,6 +395,58 @@ void launch_quantiles(hipStream_t st, const double* F, int S, int64_t n, int64_t
                       int64_t ld_r, int64_t ld_c, int nq, const int* lo, const double* g,
                       double* out, int64_t ldo_q, int64_t ldo_r, int64_t ldo_c);
 
+// k_score.hip (scores against held-out targets; definitions and the canonical orders in the file
+// header)
+constexpr int kScoreRegMax = 64;    // longest list the scorer's register path takes: NP = 128
+                                    // spills beside the two sums
+constexpr int kScoreMaxL = 8;       // central levels per call
+constexpr int kScoreMaxBins = 64;   // PIT bins per call
+constexpr int kScoreChunk = 256;    // points of one output per reduction chunk
+// launches of the per-entry sample pass by path (gpar_debug_counter "score_reg" / "score_lds";
+// GPAR_SCORE_PATH=reg / lds forces one where it can serve the size)
+extern std::atomic<int64_t> g_score_reg_launches, g_score_lds_launches;
+// per-entry records, entry (i, c) at index i p + c: crps, flags (inside bits 0-7, PIT bin bits
+// 8-15, status bits 16-17: 0 scored, 1 missing, 2 bad); the sample scorer's below / equal, the
+// Gaussian scorer's x1 = log density and x2 = squared error (null for the other scorer)
+struct ScoreRec {
+  double* crps;
+  uint32_t* flags;
+  int32_t *below, *equal;
+  double *x1, *x2;
+};
+// the caller's strided per-entry device arrays (each optional), strides in elements
+struct ScoreOut {
+  double* crps;
+  int64_t ldc_r, ldc_c;
+  int32_t* below;
+  int64_t ldb_r, ldb_c;
+  int32_t* equal;
+  int64_t lde_r, lde_c;
+  double* x1;
+  int64_t ld1_r, ld1_c;
+  double* x2;
+  int64_t ld2_r, ld2_c;
+};
+// records rec_off + (i p + c) of the n x p entries of F / Y; lo / g [2 nl]: the lower and upper
+// quantile of each level (host arrays, gpar_sample_quantiles' virtual index and gamma)
+void launch_score_samples(hipStream_t st, const double* F, int S, int64_t n, int64_t p,
+                          int64_t ld_s, int64_t ld_r, int64_t ld_c, const double* Y,
+                          int64_t ldy_r, int64_t ldy_c, int nl, const int* lo, const double* g,
+                          int bins, const ScoreRec& rec, int64_t rec_off);
+// z [nl]: the levels' two-sided normal quantiles (host array)
+void launch_score_gaussian(hipStream_t st, const double* M, int64_t ldm_r, int64_t ldm_c,
+                           const double* Sd, int64_t lds_r, int64_t lds_c, const double* Y,
+                           int64_t ldy_r, int64_t ldy_c, int64_t n, int64_t p, int nl,
+                           const double* z, int bins, const ScoreRec& rec, int64_t rec_off);
+int64_t score_chunks_of(int64_t n);
+// pd: score_chunks_of(n) p 3 doubles, pi: score_chunks_of(n) p ni int32, ni = 3 + nl + bins;
+// od [c * 3 + k]: the sums of crps, x1, x2 over output c's scored entries; oi [c * ni + f]:
+// scored, missing, bad, inside[nl], hist[bins]
+void launch_score_reduce(hipStream_t st, const ScoreRec& rec, int64_t n, int64_t p, int nl,
+                         int bins, double* pd, int32_t* pi, double* od, int64_t* oi);
+void launch_score_export(hipStream_t st, const ScoreRec& rec, int64_t n, int64_t p,
+                         const ScoreOut& out);
+
 // k_exact.hip
 void launch_exact_cov(hipStream_t st, const double* x, int64_t ldx, int64_t n, const double* x2,
                       int64_t ldx2, int64_t n2, int dx, int tk, int ok, double inv_lt, double s_t,

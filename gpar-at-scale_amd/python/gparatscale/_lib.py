@@ -34,6 +34,7 @@ EXPORTED = (
     "gpar_predict_samples", "gpar_posterior_predict_samples",
     "gpar_corr_span_plan", "gpar_corr_span_psi",
     "gpar_sample_quantiles",
+    "gpar_score_samples", "gpar_score_gaussian",
 )
 
 
@@ -166,10 +167,16 @@ def load(path: str | None = None):
         sig.update({
             "gpar_sample_quantiles": (i32, [vp, i32, i64, i64, dp, i64, i64, i64, i32, dp, i32, dp,
                                             i64, i64, i64]),
+            "gpar_score_samples": (i32, [vp, i32, i64, i64, dp, i64, i64, i64, dp, i64, i64, i32,
+                                         dp, i32, i32, dp, i64, i64, vp, i64, i64, vp, i64, i64,
+                                         dp, dp, vp, vp, vp, vp]),
+            "gpar_score_gaussian": (i32, [vp, i64, i64, dp, i64, i64, dp, i64, i64, dp, i64, i64,
+                                          i32, dp, i32, i32, dp, i64, i64, dp, i64, i64, dp, i64,
+                                          i64, dp, dp, dp, dp, vp, vp, vp, vp]),
         })
         later = ("gpar_debug_counter", "gpar_predict_mean", "gpar_posterior_predict_mean",
                  "gpar_posterior_prepare_mean", "gpar_corr_span_plan", "gpar_corr_span_psi",
-                 "gpar_sample_quantiles")
+                 "gpar_sample_quantiles", "gpar_score_samples", "gpar_score_gaussian")
         for name, (res, args) in sig.items():
             if name in later and not hasattr(lib, name):
                 continue   # older builds (library A/B runs, tools/lib_bitcheck.py) lack these
@@ -212,7 +219,8 @@ def debug_counter(name):
     "gains_general" = phase-3 gains launches by kernel path; "gains_p1_lane1" / "gains_p1_lane4" =
     phase-1 gains launches by lanes per chunk (GPAR_GAINS_P1_LANES=1 / 4 forces one);
     "quantile_reg" / "quantile_lds" = sample_quantiles' launches by path (GPAR_QUANTILE_PATH=reg /
-    lds forces one)."""
+    lds forces one); "score_reg" / "score_lds" = score_samples' per-entry launches by path
+    (GPAR_SCORE_PATH=reg / lds forces one)."""
     return int(load().gpar_debug_counter(name.encode()))
 
 

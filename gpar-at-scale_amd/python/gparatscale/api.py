@@ -717,6 +717,198 @@ def sample_quantiles(F, q, out=None, device=0):
     return out
 
 
+# ----------------------------------------------------------------------------- scores
+@dataclass
+class SampleScores:
+    """score_samples' result, per output over its scored entries (host numpy arrays): crps [P] the
+    mean ensemble CRPS, coverage [L x P] the share of targets inside the central band of each
+    level, pit_hist [B x P] the counts of the mid-rank PIT bins, scored / missing / bad [P] the
+    entries that count, whose target is NaN, and whose samples hold a NaN.  levels: the central
+    levels.  With entries=True also crps_entries, below (#samples < y) and equal (#samples == y),
+    each N* (x P), numpy or torch like F; NaN / -1 at missing or bad entries."""
+    crps: np.ndarray
+    coverage: np.ndarray
+    pit_hist: np.ndarray
+    scored: np.ndarray
+    missing: np.ndarray
+    bad: np.ndarray
+    levels: tuple
+    crps_entries: object = None
+    below: object = None
+    equal: object = None
+
+
+@dataclass
+class GaussianScores:
+    """score_gaussian's result: SampleScores' aggregates (crps the mean Gaussian CRPS, pit_hist
+    from Phi(z)) plus log_density [P] and mse [P], the mean log predictive density and the mean
+    squared error over the scored entries; bad counts NaN mean / std and std <= 0.  With
+    entries=True also crps_entries, log_density_entries, sq_err_entries, each N* (x P)."""
+    crps: np.ndarray
+    log_density: np.ndarray
+    mse: np.ndarray
+    coverage: np.ndarray
+    pit_hist: np.ndarray
+    scored: np.ndarray
+    missing: np.ndarray
+    bad: np.ndarray
+    levels: tuple
+    crps_entries: object = None
+    log_density_entries: object = None
+    sq_err_entries: object = None
+
+
+def _score_tensor(a, name, dev, shape, like=None):
+    """A float64 tensor of `shape` of the memory kind `dev` names -> (address, strides in doubles),
+    a dimension of one element carrying stride 1; DomainError otherwise."""
+    kind = "torch device tensor" if dev else "numpy array"
+    if (_is_torch(a) if dev else isinstance(a, np.ndarray)) is False:
+        raise _arg_error(f"{name} must be a {kind}, as the predictions are")
+    if dev:
+        import torch
+        if a.dtype != torch.float64:
+            raise _arg_error(f"{name} must be float64")
+        if not a.is_cuda:
+            raise _arg_error("torch tensors must be device tensors (host data: numpy arrays)")
+        if like is not None and a.device != like.device:
+            raise _arg_error(f"{name} must live on the predictions' device")
+    elif a.dtype != np.float64:
+        raise _arg_error(f"{name} must be float64")
+    if shape is not None and tuple(int(x) for x in a.shape) != tuple(shape):
+        raise _arg_error(f"{name} must have shape {tuple(shape)}")
+    if dev:
+        ld = [int(x) for x in a.stride()]
+    elif any(x % 8 for x in a.strides):
+        raise _arg_error("strides must be multiples of 8 bytes")
+    else:
+        ld = [x // 8 for x in a.strides]
+    ld = tuple(1 if m == 1 else x for x, m in zip(ld, a.shape))
+    if ld and min(ld) < 1:
+        raise _arg_error("strides must be positive")
+    return (a.data_ptr() if dev else a.ctypes.data), ld
+
+
+def _score_options(levels, bins):
+    if levels is None:
+        raise _arg_error("levels must be a sequence of numbers in (0, 1)")
+    try:
+        la = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).ravel())
+    except (TypeError, ValueError):
+        raise _arg_error("levels must be a sequence of numbers in (0, 1)") from None
+    if la.size < 1:
+        raise _arg_error("levels must hold at least one level")
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)):
+        raise _arg_error("bins must be an integer")
+    return la, int(bins)
+
+
+def _plane2(ld, rank):
+    return ld if rank == 2 else ld + (1,)
+
+
+def score_samples(F, y, levels=(0.5, 0.9, 0.95), bins=10, entries=False, device=0):
+    """Score joint samples against held-out targets on the device (gpar_score_samples).  F: S x N*
+    or S x N* x P float64 samples, a numpy array (host memory) or a torch device tensor, any
+    positive strides (read in place, as sample_quantiles reads them); y: the targets, N* or
+    N* x P, of F's kind, NaN where nothing was observed.  Per output, over the entries with a
+    target and no NaN sample: the mean ensemble CRPS (E|X - y| - E|X - X'| / 2), the histogram over
+    `bins` bins of the mid-rank PIT (below + equal / 2) / S, and the share of targets inside the
+    central band of each level l in `levels` (at most 8, each in (0, 1)) -- the closed interval
+    between sample_quantiles' quantiles (1 - l) / 2 and (1 + l) / 2, flag for flag.  Every result
+    is bit-identical whatever the strides, the memory kind or the kernel path.  entries=True adds
+    the per-entry CRPS and ranks.  Returns SampleScores.  S <= 4096, bins <= 64."""
+    dev = _is_torch(F)
+    if not dev and not isinstance(F, np.ndarray):
+        raise _arg_error("F must be a numpy array or a torch device tensor")
+    if len(F.shape) not in (2, 3):
+        raise _arg_error("F must be S x N* or S x N* x P")
+    shape = tuple(int(x) for x in F.shape)
+    if min(shape) < 1:
+        raise _arg_error("F must not be empty")
+    fp, lf = _score_tensor(F, "F", dev, None)
+    yp, ly = _score_tensor(y, "y", dev, shape[1:], like=F)
+    la, nb = _score_options(levels, bins)
+    S, n = shape[0], shape[1]
+    p = shape[2] if len(shape) == 3 else 1
+    ctx, lib = context(device), _lib.load()
+    ce = be = ee = None
+    cp = bp = ep = None
+    if entries:
+        if dev:
+            import torch
+            ce = torch.empty(shape[1:], dtype=torch.float64, device=F.device)
+            be = torch.empty(shape[1:], dtype=torch.int32, device=F.device)
+            ee = torch.empty(shape[1:], dtype=torch.int32, device=F.device)
+            cp, bp, ep = ce.data_ptr(), be.data_ptr(), ee.data_ptr()
+        else:
+            ce = np.empty(shape[1:])
+            be = np.empty(shape[1:], dtype=np.int32)
+            ee = np.empty(shape[1:], dtype=np.int32)
+            cp, bp, ep = ce.ctypes.data, be.ctypes.data, ee.ctypes.data
+    lf3 = lf if len(shape) == 3 else lf + (1,)
+    ly2 = _plane2(ly, len(shape) - 1)
+    crps, cov = np.empty(p), np.empty((la.size, p))
+    hist = np.zeros((max(nb, 0), p), dtype=np.int64)
+    cnt = [np.zeros(p, dtype=np.int64) for _ in range(3)]
+    mem = _lib.GPAR_MEM_DEVICE if dev else _lib.GPAR_MEM_HOST
+    with _after_torch(ctx, dev):
+        ctx.check(lib.gpar_score_samples(
+            ctx.h, S, n, p, fp, lf3[0], lf3[1], lf3[2], yp, ly2[0], ly2[1], int(la.size), _ptr(la),
+            nb, mem, cp, p, 1, bp, p, 1, ep, p, 1, _ptr(crps), _ptr(cov), _ptr(hist),
+            _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
+    return SampleScores(crps, cov, hist, cnt[0], cnt[1], cnt[2], tuple(float(x) for x in la),
+                        ce, be, ee)
+
+
+def score_gaussian(mean, std, y, levels=(0.5, 0.9, 0.95), bins=10, entries=False, device=0):
+    """Score Gaussian predictions against held-out targets on the device (gpar_score_gaussian):
+    the analytic and MC modes' (mean, std), on the scale score_samples uses for sample chains.
+    mean, std, y: N* or N* x P float64, numpy arrays or torch device tensors of one kind, any
+    positive strides; y NaN where nothing was observed.  With z = (y - mean) / std, per output
+    over the entries with a target, a mean, and std > 0: the mean log density, the mean CRPS
+    std (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi)), the mean squared error, the histogram of
+    Phi(z) over `bins` bins and the share with |z| <= Phi^-1((1 + l) / 2) for each level l.  std
+    is scored as given: a prediction of the latent f scores noisy observations with
+    sqrt(std**2 + sigma_n**2).  Returns GaussianScores."""
+    dev = _is_torch(mean)
+    if not dev and not isinstance(mean, np.ndarray):
+        raise _arg_error("mean must be a numpy array or a torch device tensor")
+    if len(mean.shape) not in (1, 2):
+        raise _arg_error("mean must be N* or N* x P")
+    shape = tuple(int(x) for x in mean.shape)
+    if min(shape) < 1:
+        raise _arg_error("mean must not be empty")
+    mp_, lm = _score_tensor(mean, "mean", dev, None)
+    sp, ls = _score_tensor(std, "std", dev, shape, like=mean)
+    yp, ly = _score_tensor(y, "y", dev, shape, like=mean)
+    la, nb = _score_options(levels, bins)
+    n = shape[0]
+    p = shape[1] if len(shape) == 2 else 1
+    ctx, lib = context(device), _lib.load()
+    ent = [None] * 3
+    eptr = [None] * 3
+    if entries:
+        if dev:
+            import torch
+            ent = [torch.empty(shape, dtype=torch.float64, device=mean.device) for _ in range(3)]
+            eptr = [a.data_ptr() for a in ent]
+        else:
+            ent = [np.empty(shape) for _ in range(3)]
+            eptr = [a.ctypes.data for a in ent]
+    lm, ls, ly = (_plane2(x, len(shape)) for x in (lm, ls, ly))
+    crps, ld, mse, cov = np.empty(p), np.empty(p), np.empty(p), np.empty((la.size, p))
+    hist = np.zeros((max(nb, 0), p), dtype=np.int64)
+    cnt = [np.zeros(p, dtype=np.int64) for _ in range(3)]
+    mem = _lib.GPAR_MEM_DEVICE if dev else _lib.GPAR_MEM_HOST
+    with _after_torch(ctx, dev):
+        ctx.check(lib.gpar_score_gaussian(
+            ctx.h, n, p, mp_, lm[0], lm[1], sp, ls[0], ls[1], yp, ly[0], ly[1], int(la.size),
+            _ptr(la), nb, mem, eptr[0], p, 1, eptr[1], p, 1, eptr[2], p, 1, _ptr(crps), _ptr(ld),
+            _ptr(mse), _ptr(cov), _ptr(hist), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
+    return GaussianScores(crps, ld, mse, cov, hist, cnt[0], cnt[1], cnt[2],
+                          tuple(float(x) for x in la), ent[0], ent[1], ent[2])
+
+
 class Posterior:
     """gpar_fit_posterior's result: the fitted theta of every output and its q(u), kept on the
     device, so that predictions whose inference inputs arrive later (the chained sweep of
@@ -856,6 +1048,17 @@ class Posterior:
         reads it in place."""
         chain, means, stds = self.sample_chain(t_star, given_inputs, samples, seed=seed)
         return chain, means, stds, sample_quantiles(chain, quantiles, device=self.device)
+
+    def sample_chain_scores(self, t_star, given_inputs, samples, y_star, levels=(0.5, 0.9, 0.95),
+                            bins=10, seed=0):
+        """sample_chain scored against held-out targets: returns (samples, means, stds, scores),
+        the first three exactly sample_chain's for the same arguments, scores the SampleScores of
+        the whole chain against y_star (N* x P, of the chain's memory kind, NaN where an output
+        was not observed) -- one score_samples call after the sweep, which reads the chain in
+        place."""
+        chain, means, stds = self.sample_chain(t_star, given_inputs, samples, seed=seed)
+        return chain, means, stds, score_samples(chain, y_star, levels=levels, bins=bins,
+                                                 device=self.device)
 
     def prepare(self, i, t_star):
         """Queue output i's inference-input-independent prediction work for device test times

@@ -530,6 +530,72 @@ int32_t gpar_sample_quantiles(gpar_ctx* ctx, int32_t samples, int64_t n, int64_t
                               int32_t nq, const double* q, int32_t mem, double* out,
                               int64_t ldo_q, int64_t ldo_r, int64_t ldo_c);
 
+/* ---------------------------------------------------------------- scores against held-out data
+ * gpar_score_samples: the samples x n x p tensor f (element (s, i, c) at f[s*ld_s + i*ld_r +
+ * c*ld_c], as gpar_sample_quantiles reads it) against targets y, entry (i, c) at y[i*ldy_r +
+ * c*ldy_c]; strides in elements, all positive.  A NaN target means "not observed".  With x the
+ * ascending sort of an entry's samples, S = samples and d_k = x_k - y:
+ *   below = #{s : f_s < y}, equal = #{s : f_s == y} (exact);
+ *   PIT bin = min(bins - 1, ((2 below + equal) bins) / (2 S)), integer arithmetic on the mid-rank
+ *     PIT (below + equal / 2) / S;
+ *   crps = (1/S) sum_k |d_k| - (1/S^2) sum_k (2k - S + 1) d_k, the ensemble CRPS E|X - y| -
+ *     E|X - X'| / 2 centred on y; both sums by a binary tree over the positions padded with zeros
+ *     to a power of two (adjacent pairs first), no FMA, so the bits depend on the entry's samples
+ *     and y alone;
+ *   inside level l = Q((1 - l)/2) <= y <= Q((1 + l)/2) with Q gpar_sample_quantiles' quantile,
+ *     so the flag agrees entry for entry with the bands that call returns.
+ * An entry is scored if y and every sample are not NaN, missing if y is NaN, bad if y is present
+ * and a sample is NaN; +-inf follow IEEE arithmetic.  Per-entry outputs (each optional, NULL to
+ * skip; in `mem`, own strides; a missing or bad entry gives NaN / -1): crps_e (n x p doubles),
+ * below_e, equal_e (n x p int32).  Aggregates per output c over its scored entries, host arrays,
+ * all required: crps [p] the mean (NaN if none scored), coverage [nlevels x p] at [l*p + c] =
+ * inside count / scored, pit_hist [bins x p] at [b*p + c], scored / missing / bad [p].  The
+ * aggregates are reduced in an order that depends on (n, p) alone -- chunks of 256 points per
+ * output, a fixed tree inside a chunk, the chunks in index order -- so they do not depend on the
+ * strides, the memory kind or the kernel path.  levels [nlevels]: host, each in (0, 1), nlevels
+ * 1..8; bins 1..64.  f, y and the per-entry outputs in `mem`: device tensors are read in place
+ * (workspace: 20 bytes per entry for the records, 24 + 4 (3 + nlevels + bins) bytes per 256-point
+ * chunk and output for the partials; nothing of f's size); host tensors are staged in blocks of
+ * at most 256 MB and reduced once, giving the device call's bits.  samples <= 128: one lane per
+ * entry in registers; up to 4096: a workgroup in LDS (gpar_debug_counter "score_reg" /
+ * "score_lds"; GPAR_SCORE_PATH=reg / lds forces one, for tests); both give the same bits.
+ * GPAR_ERR_ARG, before any launch, for samples, n or p < 1, p > 2^28, a level outside (0, 1) or
+ * NaN, nlevels or bins out of range, a NULL required pointer, a non-positive stride, strides under
+ * which two elements of one tensor share an address, an unknown mem; GPAR_ERR_UNSUPPORTED for
+ * samples > 4096.  Event-timing families "score" (the per-entry pass; gpar_ctx_kernel_work: HBM
+ * bytes, 8 samples n p) and "score_reduce". */
+int32_t gpar_score_samples(gpar_ctx* ctx, int32_t samples, int64_t n, int64_t p, const double* f,
+                           int64_t ld_s, int64_t ld_r, int64_t ld_c, const double* y,
+                           int64_t ldy_r, int64_t ldy_c, int32_t nlevels, const double* levels,
+                           int32_t bins, int32_t mem, double* crps_e, int64_t ldc_r,
+                           int64_t ldc_c, int32_t* below_e, int64_t ldb_r, int64_t ldb_c,
+                           int32_t* equal_e, int64_t lde_r, int64_t lde_c, double* crps,
+                           double* coverage, int64_t* pit_hist, int64_t* scored,
+                           int64_t* missing, int64_t* bad);
+/* gpar_score_gaussian: Gaussian predictions mean / std (entry (i, c) at mean[i*ldm_r + c*ldm_c],
+ * std[i*lds_r + c*lds_c]) against y, with z = (y - mean) / std:
+ *   log density = -log(2 pi std^2) / 2 - z^2 / 2;
+ *   crps = std (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi));
+ *   squared error = (y - mean)^2;
+ *   inside level l = |z| <= Phi^-1((1 + l)/2) (the quantile computed on the host);
+ *   PIT bin = min(bins - 1, floor(Phi(z) bins)).
+ * missing: y NaN; bad: mean or std NaN, or std <= 0.  std is the caller's: pass
+ * sqrt(std_f^2 + sigma_n^2) to score noisy observations rather than the latent f.  Per-entry
+ * outputs (optional, in `mem`, own strides, NaN for missing or bad entries): crps_e, logdens_e,
+ * sqerr_e.  Aggregates as gpar_score_samples', plus log_density [p] and mse [p] (means over the
+ * scored entries), in the same fixed order.  Workspace 28 bytes per entry plus the partials.
+ * Levels, bins, strides, mem and the errors as gpar_score_samples'.  Event-timing families
+ * "score_gauss" (24 n p bytes) and "score_reduce". */
+int32_t gpar_score_gaussian(gpar_ctx* ctx, int64_t n, int64_t p, const double* mean,
+                            int64_t ldm_r, int64_t ldm_c, const double* std, int64_t lds_r,
+                            int64_t lds_c, const double* y, int64_t ldy_r, int64_t ldy_c,
+                            int32_t nlevels, const double* levels, int32_t bins, int32_t mem,
+                            double* crps_e, int64_t ldc_r, int64_t ldc_c, double* logdens_e,
+                            int64_t ldl_r, int64_t ldl_c, double* sqerr_e, int64_t ldq_r,
+                            int64_t ldq_c, double* crps, double* log_density, double* mse,
+                            double* coverage, int64_t* pit_hist, int64_t* scored,
+                            int64_t* missing, int64_t* bad);
+
 /* ---------------------------------------------------------------- temporal-only (LGSSM) chains
  * `nchains` independent chains sharing the time grid t [n] (ascending); chain c's
  * observations at y[c*ldy + k].  theta: nchains x 3 natural (l, process_var, noise_sigma)

@@ -27,6 +27,10 @@ and the quantiles of such samples over the sample axis (credible bands):
 
   sample_quantiles                   -> bands
 
+and the scores of predictions against held-out targets (CRPS, PIT histogram, coverage):
+
+  sample_scores, gaussian_scores     -> NamedTuple of per-output aggregates
+
 with every number computed by the gfx950 kernels behind include/gpar_hip.h.  A caller switches
 `using GPARatScale` to `using GPARatScale, GPARatScaleHIP` and qualifies these five names (or
 imports them from GPARatScaleHIP).  The reference's helpers (to_ColVecs, unpack_gpar,
@@ -51,7 +55,8 @@ using GPARatScale: to_ColVecs, unpack_gpar, unpack_gp, parse_initial_gpar_params
 
 export compute_gpar_dtc_objective, get_optim_scaled_gpar_params, compute_q_u,
        get_gpar_scaled_predictions, get_sde_predictions, get_gpar_scaled_predictions_batch,
-       select_pseudo_inputs, get_gpar_scaled_prediction_samples, sample_quantiles
+       select_pseudo_inputs, get_gpar_scaled_prediction_samples, sample_quantiles,
+       sample_scores, gaussian_scores
 
 const libgpar = get(ENV, "GPAR_HIP_LIB", "libgparhip.so")
 
@@ -424,6 +429,105 @@ function sample_quantiles(F::StridedArray{Float64}, q)
                        Int64(ns)))
     end
     return out
+end
+
+# ------------------------------------------------------------------ scores against held-out data
+function _score_options(levels, bins)
+    ls = Vector{Float64}(collect(levels))
+    1 <= length(ls) <= 8 || throw(DomainError(length(ls), "levels must hold 1 to 8 levels"))
+    all(x -> 0.0 < x < 1.0, ls) || throw(DomainError(ls, "every level must be in (0, 1)"))
+    1 <= bins <= 64 || throw(DomainError(bins, "bins must be in 1..64"))
+    return ls
+end
+
+"""
+    sample_scores(F, y; levels = (0.5, 0.9, 0.95), bins = 10)
+
+Scores of joint samples against held-out targets (gpar_score_samples): `F` an N* x S matrix (or
+N* x P x S array) of samples as sample_quantiles takes it, `y` the N* (N* x P) targets, NaN where
+nothing was observed; strided Float64 arrays are read where they are.  Returns a NamedTuple of
+per-output aggregates over the entries with a target and no NaN sample: `crps` (mean ensemble
+CRPS), `coverage` (P x L, the share of targets inside the central band of each level, the closed
+interval between sample_quantiles' quantiles (1 - l) / 2 and (1 + l) / 2), `pit_hist` (P x bins,
+counts of the mid-rank PIT), `scored`, `missing`, `bad`.  At most 4096 samples.
+"""
+function sample_scores(F::StridedArray{Float64}, y::StridedArray{Float64};
+                       levels = (0.5, 0.9, 0.95), bins::Integer = 10)
+    ndims(F) == 2 || ndims(F) == 3 ||
+        throw(DomainError(ndims(F), "F must be N* x S or N* x P x S"))
+    ls = _score_options(levels, bins)
+    ns, P, S = size(F, 1), ndims(F) == 3 ? size(F, 2) : 1, size(F, ndims(F))
+    min(ns, P, S) >= 1 || throw(DomainError(size(F), "F must not be empty"))
+    size(y) == size(F)[1:end-1] || throw(DomainError(size(y), "y must have F's leading shape"))
+    ldr = Int64(stride(F, 1))
+    ldc = ndims(F) == 3 ? Int64(stride(F, 2)) : Int64(1)
+    lds = Int64(stride(F, ndims(F)))
+    ldyr = Int64(stride(y, 1))
+    ldyc = ndims(y) == 2 ? Int64(stride(y, 2)) : Int64(1)
+    L = length(ls)
+    crps, coverage, pit_hist = zeros(P), zeros(P, L), zeros(Int64, P, bins)
+    scored, missing_, bad = zeros(Int64, P), zeros(Int64, P), zeros(Int64, P)
+    c = ctx()
+    GC.@preserve F y ls crps coverage pit_hist scored missing_ bad begin
+        check(c, ccall((:gpar_score_samples, libgpar), Int32,
+                       (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64,
+                        Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}, Int32, Int32,
+                        Ptr{Float64}, Int64, Int64, Ptr{Int32}, Int64, Int64, Ptr{Int32}, Int64,
+                        Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                        Ptr{Int64}),
+                       c.h, Int32(S), Int64(ns), Int64(P), pointer(F), lds, ldr, ldc, pointer(y),
+                       ldyr, ldyc, Int32(L), pointer(ls), Int32(bins), GPAR_MEM_HOST,
+                       Ptr{Float64}(C_NULL), Int64(1), Int64(1), Ptr{Int32}(C_NULL), Int64(1),
+                       Int64(1), Ptr{Int32}(C_NULL), Int64(1), Int64(1), pointer(crps),
+                       pointer(coverage), pointer(pit_hist), pointer(scored), pointer(missing_),
+                       pointer(bad)))
+    end
+    return (crps = crps, coverage = coverage, pit_hist = pit_hist, scored = scored,
+            missing = missing_, bad = bad, levels = ls)
+end
+
+"""
+    gaussian_scores(mean, std, y; levels = (0.5, 0.9, 0.95), bins = 10)
+
+Scores of Gaussian predictions against held-out targets (gpar_score_gaussian): `mean`, `std`, `y`
+N* vectors or N* x P matrices, `y` NaN where nothing was observed.  Returns sample_scores'
+aggregates (the Gaussian CRPS, the histogram of Phi(z), coverage of |z| <= Phi^-1((1 + l) / 2))
+plus `log_density` and `mse`.  `std` is scored as given: pass sqrt.(std .^ 2 .+ sigma_n^2) to
+score noisy observations rather than the latent f.
+"""
+function gaussian_scores(mean::StridedArray{Float64}, std::StridedArray{Float64},
+                         y::StridedArray{Float64}; levels = (0.5, 0.9, 0.95),
+                         bins::Integer = 10)
+    ndims(mean) == 1 || ndims(mean) == 2 ||
+        throw(DomainError(ndims(mean), "mean must be N* or N* x P"))
+    ls = _score_options(levels, bins)
+    size(std) == size(mean) && size(y) == size(mean) ||
+        throw(DomainError(size(y), "mean, std and y must have one shape"))
+    ns, P = size(mean, 1), ndims(mean) == 2 ? size(mean, 2) : 1
+    min(ns, P) >= 1 || throw(DomainError(size(mean), "mean must not be empty"))
+    ldc(a) = ndims(a) == 2 ? Int64(stride(a, 2)) : Int64(1)
+    L = length(ls)
+    crps, logd, mse = zeros(P), zeros(P), zeros(P)
+    coverage, pit_hist = zeros(P, L), zeros(Int64, P, bins)
+    scored, missing_, bad = zeros(Int64, P), zeros(Int64, P), zeros(Int64, P)
+    c = ctx()
+    GC.@preserve mean std y ls crps logd mse coverage pit_hist scored missing_ bad begin
+        check(c, ccall((:gpar_score_gaussian, libgpar), Int32,
+                       (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                        Int64, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}, Int32, Int32,
+                        Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64},
+                        Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                       c.h, Int64(ns), Int64(P), pointer(mean), Int64(stride(mean, 1)), ldc(mean),
+                       pointer(std), Int64(stride(std, 1)), ldc(std), pointer(y),
+                       Int64(stride(y, 1)), ldc(y), Int32(L), pointer(ls), Int32(bins),
+                       GPAR_MEM_HOST, Ptr{Float64}(C_NULL), Int64(1), Int64(1),
+                       Ptr{Float64}(C_NULL), Int64(1), Int64(1), Ptr{Float64}(C_NULL), Int64(1),
+                       Int64(1), pointer(crps), pointer(logd), pointer(mse), pointer(coverage),
+                       pointer(pit_hist), pointer(scored), pointer(missing_), pointer(bad)))
+    end
+    return (crps = crps, log_density = logd, mse = mse, coverage = coverage,
+            pit_hist = pit_hist, scored = scored, missing = missing_, bad = bad, levels = ls)
 end
 
 # ------------------------------------------------------------------ the GPAR per-output driver loop
